@@ -13,11 +13,23 @@ generation, loading and BVH build happen before the timed region.
 the pixel-centre camera ray for every sample (Renderer.h:805-808), the GPU traces it once per pixel
 per chunk, and `mrays_reference_equivalent_per_s` counts it once per sample as the reference does.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+      the plain run: scene set-up, W warm-up steps, K timed steps, one JSON line with the headline
+      figure (`value`, `ms_per_step`, the ray counts and the workload); nothing else runs.
+      --dump-outputs DIR writes what the timed steps left on the film (what RayTracer.film() hands
+      a caller after them) as DIR/film.npy (float32 sums, height x width x 3) and DIR/spp.npy; values
+      that are not finite are written as 0 and marked in DIR/film_nonfinite.npy; a film whose arrays
+      would pass the 64 MB cap is written as a fixed seeded sample of its pixels (DIR/film_pixels.npy holds
+      their indices). Scene, seeds and samples depend on the arguments alone, so two builds run with
+      the same arguments can be compared array for array.
       N > 1 without torchrun: one process drives N GPUs through the native group (rtg_group_*:
       one handle and host thread per device, ncclCommInitAll + the own-tile exchange of the film),
       the path an RTBase C++ host takes. N must not exceed the visible devices (exit status 2 otherwise).
-  python bench.py --devices 0,0 [--verify-film]
+  python bench.py --full ...
+      the plain run plus every other leg, after the timed steps: the kernels' times (per-launch HIP
+      events over further steps), the counting passes and rooflines, the drop-in frame loop, the
+      --shard-of exchange rehearsal, --verify-film and the CPU baseline, all in the same JSON line.
+  python bench.py --full --devices 0,0 [--verify-film]
       the same group path over an explicit device list; repeats rehearse N ranks on one GPU
   torchrun --nproc-per-node N bench.py --gpus N ...      (one process per GPU, RCCL via torch)
 """
@@ -167,6 +179,13 @@ def parse():
     # sampler sees a busy GPU), one or a few frames on the long configs
     p.add_argument("--steps", type=int, default=None)
     p.add_argument("--warmup", type=int, default=None)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also run every other leg (kernel times, counting passes and "
+                        "rooflines, drop-in frame loop, exchange rehearsal, --verify-film, CPU baseline); off: "
+                        "set-up, warm-up, the timed steps and the result line only")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the film the timed steps computed (RayTracer.film() after the last one) as "
+                        "DIR/film.npy and DIR/spp.npy")
     p.add_argument("--width", type=int, default=0, help="0 = the config's")
     p.add_argument("--height", type=int, default=0, help="0 = the config's")
     p.add_argument("--spp", type=int, default=0, help="0 = the config's")
@@ -192,6 +211,8 @@ def parse():
                         "the per-launch HIP events in a block of steps of their own; full: rounds 1-5's timed "
                         "step (film clear, a waited-for render with per-launch events, stats read back, per step)")
     a = p.parse_args()
+    if a.verify_film and not a.full:
+        p.error("--verify-film is one of the legs of --full")
     c = CONFIGS[a.config]
     if a.steps is None:
         a.steps = {"C2": 200, "C3": 120, "C4": 3, "C5": 1}[a.config]
@@ -344,9 +365,97 @@ def main():
     elapsed = time.perf_counter() - t_start
     queued[0] = False
     timing_xch[0] = False
-    kernel_timing = {"source": "per-launch HIP events on the render streams, in the timed steps"}
     if lean:
         add_stats(rt.stats())
+    if a.dump_outputs:
+        # the film as the timed steps left it, before any other leg clears it: the reduced film on
+        # rank 0 under torchrun, else what RayTracer.film() / the group's film() returns
+        if world > 1:
+            spp_done = rt.film()[1]
+            if rank == 0:
+                dump_outputs(a.dump_outputs, film_t.cpu().numpy(), spp_done)
+        else:
+            dump_outputs(a.dump_outputs, *rt.film())
+
+    if group_devs is not None:
+        parallelism = ("tile-sharded x%d, one process (rtg_group: a handle and host thread per device) + "
+                       "own-tile film exchange over %s" % (len(group_devs), "RCCL ncclSend/ncclRecv" if rt.g.uses_rccl
+                                                           else "device copies (repeated devices)"))
+    elif world > 1:
+        parallelism = ("tile-sharded x%d (torchrun ranks) + own-tile film exchange over %s"
+                       % (world, "RCCL" if backend == "nccl" else backend))
+    elif a.shard_of > 1:
+        parallelism = "one GPU rendering rank 0's tiles of %d (shard-of diagnostic, no exchange)" % a.shard_of
+    else:
+        parallelism = "one GPU, every tile (no exchange)"
+
+    def headline(rays, rays_traced, paths, t_max):
+        """The fields every result line starts with: the headline figure of the timed steps (ray and
+        path counts summed over the ranks, t_max the slowest rank's timed region) and its workload."""
+        ms_step = t_max * 1e3 / a.steps
+        return {
+            "metric": ("Mray/s (traced closest-hit + shadow rays) at 1024x1024x64spp, synthetic 1M triangles"
+                       if a.config == "C3" else "Mray/s (traced closest-hit + shadow rays), config %s" % a.config),
+            "value": round(rays_traced / t_max / 1e6, 2),
+            "unit": "Mray/s",
+            "n_gpus": world if group_devs is None else len(set(group_devs)),
+            **({"ranks": len(group_devs)} if group_devs is not None else {}),
+            "steps": a.steps,
+            "warmup": a.warmup,
+            "ms_per_step": round(ms_step, 3),
+            "ms_per_frame": round(ms_step / a.spp, 4),
+            "mpaths_per_s": round(paths / t_max / 1e6, 2),
+            "rays_per_path": round(rays / max(paths, 1), 4),
+            "rays_traced_per_path": round(rays_traced / max(paths, 1), 4),
+            "mrays_traced_per_s": round(rays_traced / t_max / 1e6, 2),
+            "mrays_reference_equivalent_per_s": round(rays / t_max / 1e6, 2),
+            "rays_note": ("value counts the rays the traversal traced. renderTile casts the pixel-centre camera "
+                          "ray for every sample (Renderer.h:805-808), so the GPU traces it once per pixel per "
+                          "chunk and the samples share its hit (same film bits); "
+                          "mrays_reference_equivalent_per_s counts it once per sample, as the reference casts "
+                          "it (rays_per_path)"),
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": ("synthetic (splitmix64 random triangles, generated in-run)" if cfg["scene"] is None
+                     else "reference scene assets (%s%s)" % (cfg["scene"], ", filtered" if cfg.get("skip_missing") else "")),
+            **({"shard_of": a.shard_of} if a.shard_of > 1 else {}),
+            "config": {"workload": "%s: %s, %dx%d, %d spp, MAX_DEPTH %d" % (
+                           a.config, "synth-1M" if cfg["scene"] is None else cfg["scene"] + ("_f" if cfg.get("skip_missing") else ""),
+                           a.width, a.height, a.spp, a.max_depth),
+                       "triangles": scene.desc.n_tris, "width": a.width, "height": a.height, "spp": a.spp,
+                       "chunk_spp": chunk_spp,
+                       "max_depth": a.max_depth,
+                       "parallelism": parallelism},
+            "timed_step": ("lean: queued renders (frame pipeline)%s, film cleared once before, ray counts read once "
+                           "after" % (" + film exchanges" if world > 1 else "")) if lean else
+                          "full: film clear + render with per-launch events + stats read-back per step",
+            "full": a.full,
+        }
+
+    if not a.full:
+        # the plain run ends here: the timed steps' ray counts (summed over the ranks) and the result line
+        sums = np.array([ext_rays, shadow_rays, paths, ext_rays - paths + cam_traced], dtype=np.float64)
+        t_max = elapsed
+        if world > 1:
+            import torch
+            tt = torch.tensor(sums, dtype=torch.float64, device=coll_dev)
+            dist.all_reduce(tt, op=dist.ReduceOp.SUM)
+            sums = tt.cpu().numpy()
+            te = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
+            dist.all_reduce(te, op=dist.ReduceOp.MAX)
+            t_max = float(te.item())
+        if rank == 0:
+            out = headline(sums[0] + sums[1], sums[3] + sums[1], sums[2], t_max)
+            out["setup_s"] = round(setup_s, 2)
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    kernel_timing = {"source": "per-launch HIP events on the render streams, in the timed steps"}
+    if lean:
         # the kernels' times: per-launch HIP events on the render streams over further steps of the
         # same workload (renders only), scaled to the timed steps
         rt.set_options(flags=base | N.RTG_OPT_TIMING)
@@ -438,9 +547,6 @@ def main():
         if len(set(group_devs)) > 1:
             group_info["note"] = ("distinct-device group: ranks render concurrently, own tiles sent to device 0 by RCCL; "
                                   "film_reduce_bit_exact (--verify-film) is its check on this run")
-        group_parallelism = ("tile-sharded x%d, one process (rtg_group: a handle and host thread per device) + "
-                             "own-tile film exchange over %s" % (len(group_devs), "RCCL ncclSend/ncclRecv" if rt.g.uses_rccl
-                                                                 else "device copies (repeated devices)"))
         if group_reduced is not None:
             # the group's device memory goes first (ranks rehearsed on one device hold a chunk each)
             del rt
@@ -610,44 +716,7 @@ def main():
 
     if rank == 0:
         out = {
-            "metric": ("Mray/s (traced closest-hit + shadow rays) at 1024x1024x64spp, synthetic 1M triangles"
-                       if a.config == "C3" else "Mray/s (traced closest-hit + shadow rays), config %s" % a.config),
-            "value": round(mrays_traced, 2),
-            "unit": "Mray/s",
-            "n_gpus": world if group_devs is None else len(set(group_devs)),
-            **({"ranks": len(group_devs)} if group_devs is not None else {}),
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": round(ms_step, 3),
-            "ms_per_frame": round(ms_step / a.spp, 4),
-            "mpaths_per_s": round(paths / t_max / 1e6, 2),
-            "rays_per_path": round(rays / max(paths, 1), 4),
-            "rays_traced_per_path": round(rays_traced / max(paths, 1), 4),
-            "mrays_traced_per_s": round(mrays_traced, 2),
-            "mrays_reference_equivalent_per_s": round(mrays, 2),
-            "rays_note": ("value counts the rays the traversal traced. renderTile casts the pixel-centre camera "
-                          "ray for every sample (Renderer.h:805-808), so the GPU traces it once per pixel per "
-                          "chunk and the samples share its hit (same film bits); "
-                          "mrays_reference_equivalent_per_s counts it once per sample, as the reference casts "
-                          "it (rays_per_path)"),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": ("synthetic (splitmix64 random triangles, generated in-run)" if cfg["scene"] is None
-                     else "reference scene assets (%s%s)" % (cfg["scene"], ", filtered" if cfg.get("skip_missing") else "")),
-            **({"shard_of": a.shard_of} if a.shard_of > 1 else {}),
-            "config": {"workload": "%s: %s, %dx%d, %d spp, MAX_DEPTH %d" % (
-                           a.config, "synth-1M" if cfg["scene"] is None else cfg["scene"] + ("_f" if cfg.get("skip_missing") else ""),
-                           a.width, a.height, a.spp, a.max_depth),
-                       "triangles": scene.desc.n_tris, "width": a.width, "height": a.height, "spp": a.spp,
-                       "chunk_spp": chunk_spp,
-                       "max_depth": a.max_depth,
-                       "parallelism": (group_parallelism if group_devs is not None else
-                                       "tile-sharded x%d (torchrun ranks) + own-tile film exchange over %s"
-                                       % (world, "RCCL" if backend == "nccl" else backend) if world > 1 else
-                                       "one GPU rendering rank 0's tiles of %d (shard-of diagnostic, no exchange)" % a.shard_of
-                                       if a.shard_of > 1 else "one GPU, every tile (no exchange)")},
+            **headline(rays, rays_traced, paths, t_max),
             # headline roofline: a hardware peak. SURVEY.md 8d's algorithmic bytes of k_trace (with the
             # box / triangle tests of the walk it runs) per launch / its average launch time, against
             # the L2 aggregate bandwidth that serves them (the ~70 MB hot scene lives in L2 + Infinity
@@ -768,9 +837,6 @@ def main():
                                               "from profiles/, not measured in this run" % os.path.relpath(pmc_path, ROOT))},
             "kernel_ms_per_step_rank0": {"trace": round(local_kernel_ms[0] / a.steps, 2),
                                          "generate_shade_accumulate": round(local_kernel_ms[2] / a.steps, 2)},
-            "timed_step": ("lean: queued renders (frame pipeline)%s, film cleared once before, ray counts read once "
-                           "after" % (" + film exchanges" if world > 1 else "")) if lean else
-                          "full: film clear + render with per-launch events + stats read-back per step",
             "kernel_timing": kernel_timing,
             "cpu_baseline": cpu,
             # one unit on both sides: the CPU's rays are the reference's (a camera ray per sample), so
@@ -795,6 +861,31 @@ def main():
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_CAP_BYTES = 64 << 20   # --dump-outputs writes at most this much in all
+DUMP_SAMPLE_SEED = 20251015  # the pixel sample of a film over the cap
+
+
+def dump_outputs(out_dir, film, spp):
+    """--dump-outputs: the film sums (float32, height x width x 3) and the sample count a caller of
+    film() receives, as out_dir/film.npy and out_dir/spp.npy. The written arrays are finite: a
+    value of the film that is not (C3's film holds NaN in some pixels, and the CPU oracle's film
+    holds them in the same ones) is written as 0 in film.npy and marked in
+    film_nonfinite.npy, same shape: 0 finite, 1 NaN, 2 +inf, 3 -inf. A film over the cap is
+    written as rows of a fixed seeded choice of pixels, (n, 3), their flat indices in film_pixels.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    film = np.ascontiguousarray(film, np.float32)
+    if 2 * film.nbytes + 4096 > DUMP_CAP_BYTES:
+        flat = film.reshape(-1, 3)
+        n = min(len(flat), DUMP_CAP_BYTES // 2 // (12 + 12 + 8))  # value, mark (float32 x 3 each), float64 index
+        pix = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(len(flat), n, replace=False))
+        np.save(os.path.join(out_dir, "film_pixels.npy"), pix.astype(np.float64))
+        film = flat[pix]
+    mark = np.select([np.isnan(film), film == np.inf, film == -np.inf], [1, 2, 3], 0).astype(np.float32)
+    np.save(os.path.join(out_dir, "film.npy"), np.where(mark == 0, film, np.float32(0)))
+    np.save(os.path.join(out_dir, "film_nonfinite.npy"), mark)
+    np.save(os.path.join(out_dir, "spp.npy"), np.array([spp], np.float64))
 
 
 def dropin_leg(rt, a, tiles, base_flags):

@@ -211,7 +211,111 @@ def tonemap_fixture():
     np.savez_compressed(os.path.join(GOLD, "tonemap_kat.npz"), **out)
 
 
+
+# ---- reduced copies of the large reference scenes (tests/golden/scenes/<name>-small) ----
+# The GPU parity tests render coffee_f, bathroom_f and materialball_f; the reference's folders hold
+# 14 / 51 / 4 MB. These are subsets small enough to commit (every file far below 1 MiB): scene.json
+# keeps the camera and the chosen instances unchanged, meshes and textures are byte copies, and the
+# two files of materialball that are too large on their own are thinned (every 4th triangle of
+# Mesh001.gem, envmap.hdr box-filtered to half size). Tests compare renderers on the same scene, so
+# a subset checks the same code paths: textures (PNG, JPEG), every BSDF kind, area and env lights.
+SMALL_BUDGET = {"coffee": 1300 << 10, "bathroom": 1800 << 10}
+SMALL_MESH_CAP = {"coffee": 400 << 10, "bathroom": 160 << 10}
+GEM_MAGIC = 4058972161
+GEM_VERTEX = 44  # GEMStaticVertex on disk
+
+
+def thin_gem(src, dst, keep_every):
+    """Copy a static .gem keeping every `keep_every`-th triangle of each mesh (unused vertices dropped)."""
+    import struct
+    b = open(src, "rb").read()
+    magic, animated, n_meshes = struct.unpack_from("<III", b, 0)
+    assert magic == GEM_MAGIC and not animated
+    at, out = 12, [struct.pack("<III", magic, 0, n_meshes)]
+    for _ in range(n_meshes):
+        start = at
+        (n_props,) = struct.unpack_from("<I", b, at)
+        at += 4
+        for _ in range(2 * n_props):
+            (ln,) = struct.unpack_from("<i", b, at)
+            at += 4 + ln
+        out.append(b[start:at])
+        (nv,) = struct.unpack_from("<I", b, at)
+        at += 4
+        verts = np.frombuffer(b, np.uint8, nv * GEM_VERTEX, at).reshape(nv, GEM_VERTEX)
+        at += nv * GEM_VERTEX
+        (ni,) = struct.unpack_from("<I", b, at)
+        at += 4
+        idx = np.frombuffer(b, np.uint32, ni, at).reshape(-1, 3)[::keep_every]
+        at += ni * 4
+        used, inv = np.unique(idx, return_inverse=True)
+        out += [struct.pack("<I", len(used)), verts[used].tobytes(), struct.pack("<I", inv.size),
+                inv.astype(np.uint32).tobytes()]
+    open(dst, "wb").write(b"".join(out))
+
+
+def small_scene_fixtures():
+    import shutil
+    from raytracingrenderer_amd import read_hdr, save_hdr
+    for name in ("coffee", "bathroom", "materialball"):
+        src, dst = os.path.join(REF, name), os.path.join(GOLD, "scenes", name + "-small")
+        os.makedirs(dst, exist_ok=True)
+        scene = json.load(open(os.path.join(src, "scene.json")))
+        size = lambda f: os.path.getsize(os.path.join(src, f))
+        have = [i for i in scene["instances"]
+                if all(os.path.exists(os.path.join(src, f)) for f in (i["filename"], i.get("reflectance", "")))]
+        if name == "materialball":
+            keep = have
+        else:
+            # lights first, then one round over the BSDF kinds and texture formats at a time, smallest
+            # meshes first, until the byte budget is spent
+            cand = [i for i in have if size(i["filename"]) <= SMALL_MESH_CAP[name] and size(i["reflectance"]) <= 512 << 10]
+            kind = lambda i: (i["bsdf"], os.path.splitext(i["reflectance"])[1])
+            groups = {}
+            for i in sorted(cand, key=lambda i: size(i["filename"])):
+                groups.setdefault(kind(i), []).append(i)
+            keep, files, spent = [i for i in cand if "emission" in i], set(), 0
+            order = [i for i in keep]
+            while any(groups.values()):
+                for k in sorted(groups):
+                    if groups[k]:
+                        order.append(groups[k].pop(len(groups[k]) // 2 if len(order) % 2 else 0))
+            keep = []
+            for i in order:
+                if any(i is j for j in keep):
+                    continue
+                add = sum(size(f) for f in {i["filename"], i["reflectance"]} - files)
+                if spent + add > SMALL_BUDGET[name]:
+                    continue
+                keep.append(i)
+                files |= {i["filename"], i["reflectance"]}
+                spent += add
+            keep = [i for i in have if any(i is j for j in keep)]  # the scene's own order
+        for i in keep:
+            for f in (i["filename"], i["reflectance"]):
+                if not os.path.exists(os.path.join(dst, f)) and size(f) <= 1000 << 10:
+                    shutil.copyfile(os.path.join(src, f), os.path.join(dst, f))
+        if name == "materialball":
+            thin_gem(os.path.join(src, "Mesh001.gem"), os.path.join(dst, "Mesh001.gem"), 4)
+            env = read_hdr(os.path.join(src, "envmap.hdr"))
+            h, w = env.shape[0] // 2 * 2, env.shape[1] // 2 * 2
+            half = env[:h, :w].reshape(h // 2, 2, w // 2, 2, 3).astype(np.float64).mean(axis=(1, 3)).astype(np.float32)
+            save_hdr(os.path.join(dst, "envmap.hdr"), half, 1)
+        if name == "coffee":
+            shutil.copyfile(os.path.join(REF, "GI.hdr"), os.path.join(dst, "GI.hdr"))
+        scene["instances"] = keep
+        with open(os.path.join(dst, "scene.json"), "w") as f:
+            json.dump(scene, f, indent=1)
+        total = sum(os.path.getsize(os.path.join(dst, f)) for f in os.listdir(dst))
+        print("%s-small: %d of %d instances, %d files, %.2f MB, largest %d KiB" % (
+            name, len(keep), len(have), len(os.listdir(dst)), total / 1e6,
+            max(os.path.getsize(os.path.join(dst, f)) for f in os.listdir(dst)) >> 10))
+
+
 if __name__ == "__main__":
+    if "--small-scenes" in sys.argv:
+        small_scene_fixtures()
+        sys.exit(0)
     if "--light-only" in sys.argv:
         light_fixtures()
     elif "--synth1m" in sys.argv:

@@ -432,13 +432,13 @@ def test_failed_group_render_poisons_until_clear():
 
 @pytest.mark.gpu
 def test_bench_native_group_rehearsal_is_bit_exact():
-    """bench.py --devices 0,0 (the native group path of --gpus N, two ranks rehearsed on one GPU)
+    """bench.py --full --devices 0,0 (the native group path of --gpus N, two ranks rehearsed on one GPU)
     reports one GPU, two ranks, and a reduced film equal to the one-device render."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--devices", "0,0", "--verify-film",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--devices", "0,0", "--verify-film",
                         "--config", "C2", "--width", "256", "--height", "192", "--spp", "4", "--steps", "1",
                         "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -10,7 +10,7 @@ import zlib
 import numpy as np
 import pytest
 
-from conftest import GOLD, SCENES, require_reference_libm, scene_path
+from conftest import GOLD, SCENES, require_reference_libm
 from oracle.pyoracle import Oracle
 from raytracingrenderer_amd import RayTracer, loadScene, write_synthetic_scene
 from raytracingrenderer_amd import _native as N
@@ -407,12 +407,14 @@ def test_c3_full_size_one_frame():
 
 
 def staged(name):
-    """Reference scene data staged into assets/ by build.stage_assets(): a missing scene is a
-    failure under -m gpu, not a skip (the C4/C5 parity cases must run on the box)."""
-    p = scene_path(name)
-    if p is None:
-        pytest.fail("%s assets missing: run raytracingrenderer_amd.build.stage_assets() where "
-                    "/root/reference exists (assets/ ships to the GPU box with the tree)" % name)
+    """The committed subset of a large reference scene (tests/golden/scenes/<name>-small, written by
+    tests/golden/make_golden.py --small-scenes: the scene's camera and a choice of its instances
+    covering its BSDF kinds, texture formats and lights; materialball's mesh thinned and its
+    environment map halved). The reference's own folders are 4-51 MB and exist only where the
+    reference tree does, so the parity cases run on these."""
+    p = os.path.join(SCENES, name + "-small")
+    if not os.path.isdir(p):
+        pytest.fail("%s is missing from the checkout" % p)
     return p
 
 

@@ -1,13 +1,13 @@
 #!/bin/bash
 # Traversal-kernel counter passes (each its own rocprofv3 --pmc run, no tracing domains).
 set -o pipefail
-R=$GRAFT_REPO_ROOT; mkdir -p $R/gpurun_out/deep; cd /tmp; export TMPDIR=/tmp
-B="$R/bench.py --no-cpu-baseline --steps 1 --warmup 0 --spp 8"
+R=$(cd "$(dirname "$0")/.." && pwd); OUT=${OUT:-$R/bench_out}; mkdir -p $OUT/deep; cd /tmp; export TMPDIR=/tmp
+B="$R/bench.py --full --no-cpu-baseline --steps 1 --warmup 0 --spp 8"
 i=0
 while read -r line; do
   [ -z "$line" ] && continue
   i=$((i+1))
-  timeout -k 10 100 rocprofv3 --pmc $line -d $R/gpurun_out/deep/p$i -o p$i --output-format csv -- python3 $B > $R/gpurun_out/deep/p$i.log 2>&1 || { echo "pass $i failed: $line"; grep -m1 "Could not\|error" $R/gpurun_out/deep/p$i.log; }
+  timeout -k 10 100 rocprofv3 --pmc $line -d $OUT/deep/p$i -o p$i --output-format csv -- python3 $B > $OUT/deep/p$i.log 2>&1 || { echo "pass $i failed: $line"; grep -m1 "Could not\|error" $OUT/deep/p$i.log; }
 done <<'PASSES'
 TA_TA_BUSY_sum TA_ADDR_STALLED_BY_TC_CYCLES_sum
 TA_DATA_STALLED_BY_TC_CYCLES_sum TA_FLAT_READ_WAVEFRONTS_sum

@@ -2,8 +2,8 @@
 # Counter passes for the wavefront kernels (each its own rocprofv3 --pmc run, no tracing domains),
 # summarised per kernel by tools/pmc_kernels.py. usage: tools/pmc_passes.sh OUTDIR [bench args]
 set -o pipefail
-R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/${1:-passes}; shift; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
-B="$R/bench.py --no-cpu-baseline --steps 1 --warmup 0 --spp 8 $*"
+R=$(cd "$(dirname "$0")/.." && pwd); OUT=${OUT:-$R/bench_out}; OUT=$OUT/${1:-passes}; shift; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
+B="$R/bench.py --full --no-cpu-baseline --steps 1 --warmup 0 --spp 8 $*"
 i=0
 while read -r line; do
   [ -z "$line" ] && continue

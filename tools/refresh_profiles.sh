@@ -3,12 +3,12 @@
 # WRITE_SIZE, DRAM requests, SQ_INSTS_VALU), their summaries (pmc_summary.py -> ${RND}_pmc_traffic.json,
 # valu_issue.py -> ${RND}_valu_issue.json, also copied to profiles/ on the box so the bench line that
 # follows reads them), then the default bench line, smoke and the side configs. Copy
-# gpurun_out/prof_out/* to profiles/ afterwards.
+# $OUT/prof_out/* to profiles/ afterwards.
 set -o pipefail
-R=$GRAFT_REPO_ROOT; cd $R; mkdir -p gpurun_out/prof_out
+R=$(cd "$(dirname "$0")/.." && pwd); OUT=${OUT:-$R/bench_out}; cd $R; mkdir -p $OUT/prof_out
 RND=${RND:-r05}
-O=$R/gpurun_out
-B="$R/bench.py --no-cpu-baseline --dropin-frames 0"
+O=$OUT
+B="$R/bench.py --full --no-cpu-baseline --dropin-frames 0"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof_kt -o kt --output-format csv -- python3 $B --steps 2 > $O/prof_kt.log 2>&1 || { echo kt failed; tail -20 $O/prof_kt.log; exit 1; }
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE -d $O/prof_fetch -o fetch --output-format csv -- python3 $B --steps 1 --warmup 0 > $O/prof_fetch.log 2>&1 || { echo fetch failed; tail -20 $O/prof_fetch.log; exit 1; }
@@ -21,7 +21,7 @@ python3 tools/valu_issue.py $O/prof_valu/valu_counter_collection.csv $O/prof_out
 cp $O/prof_out/${RND}_pmc_traffic.json $O/prof_out/${RND}_valu_issue.json profiles/
 cp $O/prof_kt/kt_kernel_stats.csv $O/prof_out/${RND}_kernel_stats.csv
 cp $O/prof_out/${RND}_kernel_stats.csv profiles/
-timeout -k 10 400 python bench.py > $O/bench.log 2>&1 || { echo bench failed; tail -20 $O/bench.log; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/bench.log 2>&1 || { echo bench failed; tail -20 $O/bench.log; exit 1; }
 tail -1 $O/bench.log | tee $O/prof_out/${RND}_bench.json
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/prof_out/${RND}_smoke.log 2>&1 || { echo smoke failed; tail -20 $O/prof_out/${RND}_smoke.log; exit 1; }
 rm -f $O/configs.jsonl

@@ -37,7 +37,8 @@ extern "C" {
  * 5: rtg_build_id; the own-tile film exchange (rtg_tile_pixels, rtg_film_gather, rtg_film_scatter),
  *    which rtg_group_reduce now uses in place of a whole-film ncclReduce; rtg_stats.chunk_samples
  * 6: rtg_group_render_async / rtg_group_reduce_async / rtg_group_synchronize (queued group frames);
- *    rtg_film_scatter takes the film's pixel count; rtg_stats.lane_idle_* appended */
+ *    rtg_film_scatter takes the film's pixel count; rtg_stats.lane_idle_* appended
+ *    (additive, still 6: the denoiser, rtg_denoise_* and rtg_group_denoise) */
 #define RTG_ABI_VERSION 6
 
 /* error codes */
@@ -330,6 +331,39 @@ int  rtg_launch_rays(rtg_handle* h, uint64_t* rays, uint32_t max, uint32_t* n);
  * step) on the device: out = {best of 3 replay ms, fetches, extension rays, shadow rays}. */
 int  rtg_debug_capture(rtg_handle* h, int launch);
 int  rtg_debug_replay(rtg_handle* h, double* out);
+
+/* ---- feature-guided film denoiser (rtg_denoise.hip). RayTracer::denoise() (Renderer.h:752-793)
+ * hands the film, the albedo and the view normals to OIDN; the reference never calls it. This is the
+ * project's own classical filter with the same inputs, not a reproduction of OIDN's output: the
+ * edge-avoiding a-trous wavelet filter (Dammertz et al. 2010). Iteration i = 0..iterations-1 filters
+ * with the 5x5 taps {1/16, 1/4, 3/8, 1/4, 1/16}^2 at step 1 << i; a tap's weight is multiplied by
+ * max(0, 1 - |dC|^2 / sc^2)^2 with sc = sigma_colour / 2^i, by max(0, 1 - |dA|^2 / sigma_albedo^2)^2,
+ * and by clamp(N[p].N[q], 0, 1) squared normal_squarings times (1 where both pixels have a zero
+ * normal: background). A sigma <= 0 switches its term off; any other must be finite and >= 1e-6.
+ * IEEE float32 without contraction in a fixed order: bit-reproducible (DESIGN.md "Denoiser").
+ * Argument errors (RTG_ERR_ARG) are reported before any device call. */
+#define RTG_DENOISE_MAX_ITERATIONS 8
+typedef struct rtg_denoise_params {
+    uint32_t iterations, normal_squarings;
+    float sigma_colour, sigma_albedo;
+} rtg_denoise_params;
+int  rtg_denoise_defaults(rtg_denoise_params* p);  /* 5, 5, 1.0f, 0.1f */
+/* The filter alone on caller-given host images (w*h*3 floats each; at most 65535 per side and 2^28
+ * pixels); out: w*h*3. */
+int  rtg_denoise_images(int device, uint32_t w, uint32_t h, const float* colour, const float* albedo,
+                        const float* normal, const rtg_denoise_params* p, float* out);
+/* film / spp of the handle, guided by the scene's own albedo and shading normals (1 sample of
+ * RTG_INTEGRATOR_ALBEDO and _NORMALS each, rendered on the first call into scratch films and cached
+ * until rtg_destroy). Issues and waits for queued frames first (as rtg_film_read); returns when the
+ * result is in the handle's device buffer, and in out (host, w*h*3) when given. The film, Film::SPP,
+ * the integrator and the options are left as they were (the call that renders the guides leaves their
+ * two renders in rtg_stats.render_ms until the next render). spp == 0: RTG_ERR_ARG. */
+int  rtg_denoise(rtg_handle* h, const rtg_denoise_params* p, float* out);
+int  rtg_denoise_guides(rtg_handle* h, float* albedo, float* normal);  /* host, w*h*3 each, either may be NULL */
+int  rtg_denoise_copy_device(rtg_handle* h, void* dst_device);         /* last result, w*h*3 floats */
+double rtg_denoise_ms(rtg_handle* h);                                  /* device time of the last rtg_denoise */
+/* Reduces if needed, then filters the assembled film on devices[0] with rank 0's guides. */
+int  rtg_group_denoise(rtg_group* g, const rtg_denoise_params* p, float* out);
 
 /* Low-level ray queries on the uploaded scene (test / oracle comparison surface).
  * rays: n*8 floats (o.xyz, tmax, dir.xyz, pad). For closest-hit, tmax is ignored and the result

@@ -62,6 +62,11 @@ class rtg_stats(C.Structure):
                 ("lane_idle_retiring", C.c_uint64), ("lane_idle_leaf_popped", C.c_uint64)]
 
 
+class rtg_denoise_params(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("normal_squarings", C.c_uint32), ("sigma_colour", C.c_float),
+                ("sigma_albedo", C.c_float)]
+
+
 class rth_load_options(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("skip_missing", C.c_int32),
                 ("bvh_threads", C.c_int32), ("envmap", C.c_char_p)]
@@ -125,6 +130,15 @@ RTG_EXPORTS = [
     ("rtg_tile_pixels", C.c_int, [C.c_uint32, C.c_uint32, u32p, C.c_uint32, u32p, u32p]),
     ("rtg_film_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("rtg_film_scatter", C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
+    # feature-guided film denoiser (rtg_denoise.hip)
+    ("rtg_denoise_defaults", C.c_int, [C.POINTER(rtg_denoise_params)]),
+    ("rtg_denoise_images", C.c_int, [C.c_int, C.c_uint32, C.c_uint32, f32p, f32p, f32p, C.POINTER(rtg_denoise_params),
+                                     f32p]),
+    ("rtg_denoise", C.c_int, [C.c_void_p, C.POINTER(rtg_denoise_params), f32p]),
+    ("rtg_denoise_guides", C.c_int, [C.c_void_p, f32p, f32p]),
+    ("rtg_denoise_copy_device", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("rtg_denoise_ms", C.c_double, [C.c_void_p]),
+    ("rtg_group_denoise", C.c_int, [C.c_void_p, C.POINTER(rtg_denoise_params), f32p]),
 ]
 
 RTH_EXPORTS = [

@@ -310,6 +310,8 @@ struct ChunkSlot {
     bool used = false;          // fold has been recorded
 };
 
+struct DenoiseState;  // rtg_denoise.hip
+
 struct rtg_handle {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -379,6 +381,7 @@ struct rtg_handle {
     unsigned* d_hcnt = nullptr;   // the same memory, device address
     int cap_cnt = 0;
     std::vector<hipEvent_t> tev;  // [b]: k_trace(b) has finished (a launch that never wrote its counts)
+    DenoiseState* dn = nullptr;   // denoiser buffers and cached guides, allocated by the first rtg_denoise*
 };
 #define RTG_CNT_PENDING 0xFFFFFFFFu
 
@@ -432,6 +435,13 @@ int launch_generate(rtg_handle* h, const ChunkArgs& a, const PathBufs& pb, hipSt
 // one k_trace launch (closest-hit rays of io.queue and any-hit rays of io.squeue) on stream st
 // (max_blocks != 0: at most that many one-wave blocks instead of the resident grid)
 int launch_trace(rtg_handle* h, const TraceIO& io, hipStream_t st, unsigned max_blocks = 0);
+// rtg_denoise.hip: filter d_sum / spp (a film on h's device) with h's guides into h's result buffer,
+// and into `out` (host) when given; waits for the result
+int denoise_film(rtg_handle* h, const float* d_sum, uint32_t spp, const rtg_denoise_params* p, float* out);
+// RTG_ERR_ARG (with "who: ..." as the message) for parameters outside include/rtg.h's ranges
+int denoise_check_params(const char* who, const rtg_denoise_params* p);
+// frees the handle's denoiser state (rtg_destroy)
+void denoise_release(rtg_handle* h);
 // rtg_shade.hip: one k_shade launch of `grid` blocks (ALT = alt, TAB = tab) for bounce b
 int launch_shade(bool alt, bool tab, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
                  const PathBufs& p, int b);

@@ -1585,6 +1585,7 @@ void rtg_destroy(rtg_handle* h) {
         if (sl.stream) (void)hipStreamDestroy(sl.stream);
     }
     if (h->entry) (void)hipEventDestroy(h->entry);
+    denoise_release(h);
     (void)hipFree(h->d_img);
     (void)hipFree(h->d_nodes); (void)hipFree(h->d_nodesq); (void)hipFree(h->d_leafbox); (void)hipFree(h->d_tris48); (void)hipFree(h->d_shade); (void)hipFree(h->d_mats);
     (void)hipFree(h->d_lights); (void)hipFree(h->d_texinfo); (void)hipFree(h->d_texels); (void)hipFree(h->d_film);

@@ -598,6 +598,20 @@ int rtg_group_clear(rtg_group* g) {
     return RTG_OK;
 }
 
+// The assembled film / spp filtered on devices[0] with rank 0's guides (rank 0's handle lives on
+// devices[0] and renders its guides over every tile); the result stays in rank 0's denoiser buffer.
+int rtg_group_denoise(rtg_group* g, const rtg_denoise_params* p, float* out) {
+    if (!g) { g_err = "rtg_group_denoise: null group"; return RTG_ERR_ARG; }
+    if (int rc = denoise_check_params("rtg_group_denoise", p)) return rc;
+    if (!g->reduced)
+        if (int rc = rtg_group_reduce_async(g)) return rc;
+    if (int rc = group_sync(g)) return rc;  // the exchange runs on its own streams
+    if (g->reduced_spp == 0) { g_err = "rtg_group_denoise: the film holds no samples (spp == 0)"; return RTG_ERR_ARG; }
+    HIPOK(hipSetDevice(g->devices[0]));
+    if (int rc = join_frames(g->h[0])) return rc;
+    return denoise_film(g->h[0], g->d_sum, g->reduced_spp, p, out);
+}
+
 double rtg_group_reduce_ms(rtg_group* g) { return g ? g->reduce_ms : 0.0; }
 
 int rtg_group_uses_rccl(rtg_group* g) { return g && !g->comms.empty() ? 1 : 0; }

@@ -14,6 +14,12 @@
 // "Frame time" is the wall time of each render call, as Main.cpp:113-117 times rt.render(); with
 // queued frames a call returns once the frame three before it has left the GPU, so in the steady
 // state it is the GPU's time per frame.
+// -denoise 1 additionally writes the denoised film (rtg_denoise: the project's own edge-avoiding
+// a-trous wavelet filter guided by albedo and normals, standing in for the reference's never-called
+// OIDN pass) as RGBE next to the normal output, with _denoised before the extension
+// (-outputFilename's name when given, else result_<spp>); optional -denoiseIterations (5),
+// -denoiseSigmaColour (1), -denoiseSigmaAlbedo (0.1). The normal output is unchanged. With -gpus /
+// -devices it goes through rtg_group_denoise.
 // Multi-GPU (one node): -gpus N renders on devices 0..N-1, -devices a,b,... on a list. Rank r
 // renders the 32x32 tiles with (tile_x + tile_y) % N == r, and the film is assembled on the first
 // device from every device's own tiles (packed, one RCCL send per device, scattered) before it is
@@ -136,6 +142,23 @@ int main(int argc, char** argv) {
                      : rth_save_hdr(filename.c_str(), info.width, info.height, film.data(), got);
         if (rc != 0) return die(png ? "savePNG" : "saveHDR", rth_last_error());
         std::printf("wrote %s\n", filename.c_str());
+    }
+    if (std::stoi(get("-denoise", "0")) != 0) {
+        rtg_denoise_params dp{};
+        rtg_denoise_defaults(&dp);
+        dp.iterations = (uint32_t)std::stoul(get("-denoiseIterations", std::to_string(dp.iterations)));
+        dp.sigma_colour = std::stof(get("-denoiseSigmaColour", std::to_string(dp.sigma_colour)));
+        dp.sigma_albedo = std::stof(get("-denoiseSigmaAlbedo", std::to_string(dp.sigma_albedo)));
+        std::vector<float> den(film.size());
+        if ((grp ? rtg_group_denoise(grp, &dp, den.data()) : rtg_denoise(rt, &dp, den.data())) != 0)
+            return die("rtg_denoise", rtg_last_error());
+        std::string base = out_given ? filename : auto_name;
+        const size_t dot = base.find_last_of('.'), slash = base.find_last_of('/');
+        if (dot != std::string::npos && (slash == std::string::npos || dot > slash)) base.erase(dot);
+        const std::string den_name = base + "_denoised.hdr";
+        if (rth_save_hdr(den_name.c_str(), info.width, info.height, den.data(), 1) != 0)  // already a mean
+            return die("saveHDR", rth_last_error());
+        std::printf("wrote %s\n", den_name.c_str());
     }
     if (rt) rtg_destroy(rt);
     if (grp) rtg_group_destroy(grp);

@@ -159,6 +159,25 @@ def read_hdr(path):
         N.rth().rth_free(C.cast(p, C.c_void_p))
 
 
+def _denoise_params(iterations, normal_squarings, sigma_colour, sigma_albedo):
+    return N.rtg_denoise_params(int(iterations), int(normal_squarings), float(sigma_colour), float(sigma_albedo))
+
+
+def denoise_images(colour, albedo, normal, device=0, iterations=5, normal_squarings=5, sigma_colour=1.0,
+                   sigma_albedo=0.1):
+    """The denoiser's filter alone (rtg_denoise_images) on caller-given (H, W, 3) float32 images: the
+    edge-avoiding a-trous wavelet filter guided by albedo and normals (include/rtg.h). Returns (H, W, 3)."""
+    c, a, n = (np.ascontiguousarray(v, np.float32) for v in (colour, albedo, normal))
+    if c.ndim != 3 or c.shape[2] != 3 or a.shape != c.shape or n.shape != c.shape:
+        raise ValueError("denoise_images: colour, albedo and normal must share one (H, W, 3) shape")
+    out = np.zeros(c.shape, np.float32)
+    p = _denoise_params(iterations, normal_squarings, sigma_colour, sigma_albedo)
+    lib = N.rtg()
+    _check(lib.rtg_denoise_images(device, c.shape[1], c.shape[0], N.ptr(c, C.c_float), N.ptr(a, C.c_float),
+                                  N.ptr(n, C.c_float), C.byref(p), N.ptr(out, C.c_float)), lib.rtg_last_error)
+    return out
+
+
 class RayTracer:
     """RayTracer (Renderer.h:31-899) backed by librtg on one GPU."""
 
@@ -302,6 +321,35 @@ class RayTracer:
         f, spp = self.film()
         save_png(filename, f, spp)
 
+    def denoise(self, iterations=5, normal_squarings=5, sigma_colour=1.0, sigma_albedo=0.1):
+        """The counterpart of RayTracer::denoise (Renderer.h:752-793, OIDN, never called by the
+        reference): film / SPP filtered on the GPU by the project's own edge-avoiding a-trous
+        wavelet filter, guided by the scene's albedo and shading normals (rtg_denoise; not a
+        reproduction of OIDN's output). Returns the (H, W, 3) float32 mean image; the film, SPP and
+        the settings stay as they were. Waits for queued frames first."""
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        p = _denoise_params(iterations, normal_squarings, sigma_colour, sigma_albedo)
+        _check(self._lib.rtg_denoise(self._h, C.byref(p), N.ptr(out, C.c_float)), self._lib.rtg_last_error)
+        return out
+
+    def guides(self):
+        """(albedo, normals): the denoiser's guide images, 1 sample of the "albedo" and "normals"
+        integrators each, rendered once per RayTracer and cached (rtg_denoise_guides)."""
+        a = np.zeros((self.height, self.width, 3), np.float32)
+        n = np.zeros((self.height, self.width, 3), np.float32)
+        _check(self._lib.rtg_denoise_guides(self._h, N.ptr(a, C.c_float), N.ptr(n, C.c_float)),
+               self._lib.rtg_last_error)
+        return a, n
+
+    def copy_denoised_to(self, device_ptr):
+        """The last denoise() result, (H, W, 3) float32, copied to device memory on this GPU
+        (rtg_denoise_copy_device; like copy_film_to)."""
+        _check(self._lib.rtg_denoise_copy_device(self._h, C.c_void_p(device_ptr)), self._lib.rtg_last_error)
+
+    def denoise_ms(self):
+        """Device time of the last denoise() (pack, iterations, unpack), in ms."""
+        return self._lib.rtg_denoise_ms(self._h)
+
     def stats(self):
         s = N.rtg_stats()
         _check(self._lib.rtg_get_stats(self._h, C.byref(s)), self._lib.rtg_last_error)
@@ -405,6 +453,14 @@ class RayTracerGroup:
         spp = C.c_uint32()
         _check(self._lib.rtg_group_film_read(self._g, N.ptr(out, C.c_float), C.byref(spp)), self._lib.rtg_last_error)
         return out, spp.value
+
+    def denoise(self, iterations=5, normal_squarings=5, sigma_colour=1.0, sigma_albedo=0.1):
+        """RayTracer.denoise() of the assembled film (reduced first if needed), filtered on devices[0]
+        with rank 0's guides (rtg_group_denoise): (H, W, 3) float32, bit-identical to one device's."""
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        p = _denoise_params(iterations, normal_squarings, sigma_colour, sigma_albedo)
+        _check(self._lib.rtg_group_denoise(self._g, C.byref(p), N.ptr(out, C.c_float)), self._lib.rtg_last_error)
+        return out
 
     def reduce_ms(self):
         return self._lib.rtg_group_reduce_ms(self._g)

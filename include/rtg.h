@@ -387,6 +387,19 @@ int  rtg_trace_visible(rtg_handle* h, const float* rays, uint32_t n, int32_t* vi
 #define RTG_MATH_ACOSF  3
 #define RTG_MATH_ATAN2F 4
 int  rtg_probe_math(int fn, const float* in, uint32_t n, float* out);
+/* Texture probe on the current device: the shading kernel's own Texture::sample (Imaging.h:72-94) and
+ * EnvironmentMap::evaluate (Lights.h:150-157) arithmetic on a caller-given texture. texels_rgb: w*h*3
+ * floats, row-major (uploaded in the device layout, RGB + pad); 1..65535 per side, at most 2^28 texels.
+ * mode: RTG_PROBE_TEX_SAMPLE (in: n*2 floats tu, tv) or RTG_PROBE_TEX_ENV (in: n*3 floats, the
+ * direction wi), optionally | RTG_PROBE_TEX_UNIFORM: the short-cut the kernels take for a texture whose
+ * texels all have the same bits (the first texel for all four taps, no fetch); such a texture only.
+ * out: n*3 floats (rgb). n <= (2^31 - 1) / 3. Argument errors (RTG_ERR_ARG) are reported before any
+ * device call. */
+#define RTG_PROBE_TEX_SAMPLE  0
+#define RTG_PROBE_TEX_ENV     1
+#define RTG_PROBE_TEX_UNIFORM 2
+int  rtg_probe_texture(int mode, const float* texels_rgb, uint32_t w, uint32_t h, const float* in, uint32_t n,
+                       float* out);
 
 #ifdef __cplusplus
 }

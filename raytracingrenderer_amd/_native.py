@@ -14,6 +14,7 @@ RTG_OPT_CULL, RTG_OPT_COUNT, RTG_OPT_TIMING, RTG_OPT_BVH2, RTG_OPT_WAVETIME, RTG
 RTG_OPT_NO_COALESCE = 64
 RTG_INTEGRATOR_PATH, RTG_INTEGRATOR_DIRECT, RTG_INTEGRATOR_ALBEDO, RTG_INTEGRATOR_NORMALS = 0, 1, 2, 3
 RTG_INTEGRATOR_DIRECT_MIS = 4
+RTG_PROBE_TEX_SAMPLE, RTG_PROBE_TEX_ENV, RTG_PROBE_TEX_UNIFORM = 0, 1, 2
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
@@ -109,6 +110,7 @@ RTG_EXPORTS = [
     ("rtg_trace_visible", C.c_int, [C.c_void_p, f32p, C.c_uint32, i32p]),
     ("rtg_probe_bsdf", C.c_int, [f32p, C.c_uint32, f32p]),
     ("rtg_probe_math", C.c_int, [C.c_int, f32p, C.c_uint32, f32p]),
+    ("rtg_probe_texture", C.c_int, [C.c_int, f32p, C.c_uint32, C.c_uint32, f32p, C.c_uint32, f32p]),
     # one node, several GPUs (rtg_multi.hip): tile stripes per device + one RCCL film reduce
     ("rtg_tiles_for_rank", C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.c_int, u32p, u32p]),
     ("rtg_group_create", C.c_int, [i32p, C.c_int, C.POINTER(rtg_scene_desc), C.POINTER(C.c_void_p)]),

@@ -239,14 +239,19 @@ RTG_D v3 uniform_sample_sphere(float r1, float r2) {
 }
 RTG_D float uniform_sphere_pdf() { return (float)(1.0 / (4.0 * RTM_PI)); }
 
-// EnvironmentMap::evaluate (Lights.h:150-157)
-RTG_D v3 env_eval(const SceneView& s, v3 wi) {
+// EnvironmentMap::evaluate (Lights.h:150-157) on a w x h texture; uni / one as in bilinear(). The
+// scene's environment (env_eval) and the texture probe (k_probe_texture) share this body.
+template <class TX>
+RTG_D v3 env_lookup(TX texel, int w, int h, v3 wi, bool uni, v3 one) {
     float u = rtm_atan2f(wi.z, wi.x);
     u = (u < 0.0f) ? (float)((double)u + 2.0 * RTM_PI) : u;
     u = div_2pi_d(u);                // (float)((double)u / (2.0 * M_PI))
     float v = div_pi_d(rtm_acosf(wi.y));  // (float)((double)acosf(wi.y) / M_PI)
-    return bilinear(Texels4{s.texels + s.env_off}, s.env_w, s.env_h, u, v, s.env_uniform != 0,
-                    mk(s.env_one[0], s.env_one[1], s.env_one[2]));
+    return bilinear(texel, w, h, u, v, uni, one);
+}
+RTG_D v3 env_eval(const SceneView& s, v3 wi) {
+    return env_lookup(Texels4{s.texels + s.env_off}, s.env_w, s.env_h, wi, s.env_uniform != 0,
+                      mk(s.env_one[0], s.env_one[1], s.env_one[2]));
 }
 RTG_D v3 background(const SceneView& s, v3 dir) {
     if (s.env_tex < 0) return mk(0.0f, 0.0f, 0.0f);  // BackgroundColour(0,0,0)::evaluate

@@ -766,6 +766,24 @@ __global__ void k_probe_bsdf(const float* in, int n, float* out) {
     o[8] = ev.x; o[9] = ev.y; o[10] = ev.z;
 }
 
+// Texture probe: k_shade's own bilinear<Texels4> (Texture::sample, as tex_sample calls it) and
+// env_lookup (EnvironmentMap::evaluate, env_eval's body) on a texture in the device layout.
+// env 0: in = (tu, tv) per case; env 1: in = dir.xyz per case. uni: the "uniform texture" short-cut
+// (every tap is the first texel, held by the caller: DevMat::texel0 / SceneView::env_one).
+__global__ void k_probe_texture(int env, int uni, const float4* texels, int w, int h, const float* in, int n,
+                                float* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 t0 = texels[0];
+    const v3 one = mk(t0.x, t0.y, t0.z);
+    const Texels4 tx{texels};
+    const v3 r = env ? env_lookup(tx, w, h, mk(in[3 * (size_t)i], in[3 * (size_t)i + 1], in[3 * (size_t)i + 2]),
+                                  uni != 0, one)
+                     : bilinear(tx, w, h, in[2 * (size_t)i], in[2 * (size_t)i + 1], uni != 0, one);
+    float* o = out + (size_t)i * 3;
+    o[0] = r.x; o[1] = r.y; o[2] = r.z;
+}
+
 // Transcendental probe: the device's include/rtg_math.h on given inputs (parity vs the host glibc).
 // fn 0 sinf, 1 cosf, 2 sincosf (out: sin, cos per input), 3 acosf, 4 atan2f (in: y, x per input).
 __global__ void k_probe_math(int fn, const float* in, int n, float* out) {
@@ -2436,6 +2454,53 @@ int rtg_probe_bsdf(const float* cases, uint32_t n, float* out) {
     (void)hipFree(d_in);
     (void)hipFree(d_out);
     return RTG_OK;
+}
+
+int rtg_probe_texture(int mode, const float* texels_rgb, uint32_t w, uint32_t h, const float* in, uint32_t n,
+                      float* out) {
+    auto bad = [](const char* what) {
+        g_err = std::string("rtg_probe_texture: ") + what;
+        return RTG_ERR_ARG;
+    };
+    if (!texels_rgb || !in || !out) return bad("null argument");
+    if (mode < 0 || mode > (RTG_PROBE_TEX_ENV | RTG_PROBE_TEX_UNIFORM)) return bad("unknown mode");
+    if (w == 0 || h == 0 || w > 0xffffu || h > 0xffffu || (uint64_t)w * h > (1ull << 28))
+        return bad("texture size must be 1..65535 per side and at most 2^28 texels");
+    if (n > 0x7fffffffu / 3u) return bad("too many cases");
+    const size_t nt = (size_t)w * h;
+    const bool env = (mode & RTG_PROBE_TEX_ENV) != 0, uni = (mode & RTG_PROBE_TEX_UNIFORM) != 0;
+    if (uni)  // the short-cut's precondition, as prepare_scene establishes it: every texel has the first one's bits
+        for (size_t j = 1; j < nt; ++j)
+            if (std::memcmp(texels_rgb + 3 * j, texels_rgb, 3 * sizeof(float)) != 0)
+                return bad("RTG_PROBE_TEX_UNIFORM needs a texture whose texels all have the same bits");
+    if (n == 0) return RTG_OK;
+    std::vector<float> t4(nt * 4);  // RGB + pad: one 16-B load per texel, as prepare_scene uploads them
+    for (size_t j = 0; j < nt; ++j) {
+        t4[4 * j] = texels_rgb[3 * j];
+        t4[4 * j + 1] = texels_rgb[3 * j + 1];
+        t4[4 * j + 2] = texels_rgb[3 * j + 2];
+        t4[4 * j + 3] = 0.0f;
+    }
+    const size_t nin = (size_t)n * (env ? 3 : 2), nout = (size_t)n * 3;
+    float *d_tex = nullptr, *d_in = nullptr, *d_out = nullptr;
+    auto run = [&]() -> int {
+        HIPOK(hipMalloc((void**)&d_tex, t4.size() * sizeof(float)));
+        HIPOK(hipMalloc((void**)&d_in, nin * sizeof(float)));
+        HIPOK(hipMalloc((void**)&d_out, nout * sizeof(float)));
+        HIPOK(hipMemcpy(d_tex, t4.data(), t4.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIPOK(hipMemcpy(d_in, in, nin * sizeof(float), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_probe_texture, dim3((n + 255) / 256), dim3(256), 0, nullptr, env ? 1 : 0, uni ? 1 : 0,
+                           (const float4*)d_tex, (int)w, (int)h, (const float*)d_in, (int)n, d_out);
+        HIPOK(hipGetLastError());
+        HIPOK(hipDeviceSynchronize());
+        HIPOK(hipMemcpy(out, d_out, nout * sizeof(float), hipMemcpyDeviceToHost));
+        return RTG_OK;
+    };
+    const int rc = run();
+    (void)hipFree(d_tex);
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    return rc;
 }
 
 int rtg_probe_math(int fn, const float* in, uint32_t n, float* out) {

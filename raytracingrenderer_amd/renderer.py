@@ -178,6 +178,23 @@ def denoise_images(colour, albedo, normal, device=0, iterations=5, normal_squari
     return out
 
 
+def probe_texture(texels, coords, env=False, uniform=False):
+    """The shading kernel's texture arithmetic alone (rtg_probe_texture, test surface) on a caller-given
+    (H, W, 3) float32 texture, on the current device. env=False: Texture::sample at coords (n, 2) = (tu,
+    tv); env=True: EnvironmentMap::evaluate at coords (n, 3), the direction. uniform=True takes the
+    kernels' short-cut for a texture whose texels all have the same bits. Returns (n, 3) float32."""
+    t = np.ascontiguousarray(texels, np.float32)
+    if t.ndim != 3 or t.shape[2] != 3:
+        raise ValueError("probe_texture: texels must be (H, W, 3)")
+    c = np.ascontiguousarray(coords, np.float32).reshape(-1, 3 if env else 2)
+    out = np.zeros((len(c), 3), np.float32)
+    mode = (N.RTG_PROBE_TEX_ENV if env else N.RTG_PROBE_TEX_SAMPLE) | (N.RTG_PROBE_TEX_UNIFORM if uniform else 0)
+    lib = N.rtg()
+    _check(lib.rtg_probe_texture(mode, N.ptr(t, C.c_float), t.shape[1], t.shape[0], N.ptr(c, C.c_float), len(c),
+                                 N.ptr(out, C.c_float)), lib.rtg_last_error)
+    return out
+
+
 class RayTracer:
     """RayTracer (Renderer.h:31-899) backed by librtg on one GPU."""
 

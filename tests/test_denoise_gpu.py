@@ -28,6 +28,10 @@ def assert_same_bits(got, want, what):
         raise AssertionError("%s: %d pixels differ, first (%d, %d): %s vs %s" % (what, len(bad), y, x, got[y, x], want[y, x]))
 
 
+def _nan_canon(a):
+    return np.where(np.isnan(a), np.float32(np.nan), a).astype(np.float32)
+
+
 def synthetic(h, w):
     """Seeded random colour with a few 1e4 outliers, an albedo step, smooth random unit normals and
     a zero-normal block."""
@@ -48,9 +52,13 @@ def synthetic(h, w):
 
 
 @pytest.mark.parametrize("sigma_colour", [0.0, 1.0])
-@pytest.mark.parametrize("iterations", [1, 2, 5, 6])
-@pytest.mark.parametrize("shape", [(1, 1), (5, 7), (33, 65), (64, 64), (70, 100)])
+@pytest.mark.parametrize("iterations", [1, 2, 5, 6, 7, 8])
+@pytest.mark.parametrize("shape", [(1, 1), (5, 7), (33, 65), (64, 64), (70, 100), (3, 260), (260, 3), (130, 270)])
 def test_filter_equals_the_reference(shape, iterations, sigma_colour):
+    """Every iteration count the API accepts (steps 1 ... 128) on shapes below, at and above a block
+    (64 x 4 pixels). An axis of 257 or more has pixels with all five taps of step 64 in bounds (260 and
+    270 here, as a single row, a single column and a 2-D image); at step 128 it puts the +-256 taps in
+    bounds, which no smaller image does."""
     c, a, n = synthetic(*shape)
     got = denoise_images(c, a, n, iterations=iterations, sigma_colour=sigma_colour)
     assert_same_bits(got, denoise_ref(c, a, n, iterations, 5, sigma_colour, 0.1), "rtg_denoise_images")
@@ -63,6 +71,22 @@ def test_filter_parameters_reach_the_kernel():
     for m, sa in [(0, 0.1), (8, 0.05), (2, 0.0)]:
         got = denoise_images(c, a, n, iterations=3, normal_squarings=m, sigma_colour=0.5, sigma_albedo=sa)
         assert_same_bits(got, denoise_ref(c, a, n, 3, m, 0.5, sa), "m=%d sigma_albedo=%g" % (m, sa))
+
+
+def test_non_finite_pixels_spread_like_the_reference():
+    """A NaN and a +inf colour pixel (33 x 65, 3 iterations, both sigma_colour settings): the stopping
+    term gives such a tap the weight 0, and 0 * NaN / 0 * inf is NaN, so the pixel's whole footprint
+    turns NaN, step by step. The device does exactly what the restatement does (any NaN equals any
+    NaN); DESIGN.md 8a states this as the filter's definition."""
+    c, a, n = synthetic(33, 65)
+    c[7, 11, 1] = np.float32(np.nan)
+    c[20, 50, :] = np.float32(np.inf)
+    for sc in (0.0, 1.0):
+        got = denoise_images(c, a, n, iterations=3, sigma_colour=sc)
+        with np.errstate(invalid="ignore", over="ignore"):
+            want = denoise_ref(c, a, n, 3, 5, sc, 0.1)
+        assert np.isnan(want).any() and np.isfinite(want).any()
+        assert_same_bits(_nan_canon(got), _nan_canon(want), "non-finite pixels, sigma_colour %g" % sc)
 
 
 @pytest.fixture(scope="module", params=["cornell-box", "coffee-small"])

@@ -377,6 +377,269 @@ def test_bsdf_probe_matches_reference_bsdfs():
     assert glass.any() and (cases[:, 0] == 0).any()
 
 
+BSDF_KIND_MAP = {0: 0, 1: 1, 2: 2, 3: 3, 4: 1, 5: 1, 6: 1}  # reference class -> rtg kind
+BSDF_IORS = [(1.5, 1.0), (1.33, 1.0), (1.0, 1.5), (2.4, 1.0), (1.5, 1.5)]  # (int, ext)
+
+
+def _unit32(v):
+    """v / |v| with the squares summed and the root taken in float32."""
+    v = np.asarray(v, np.float32)
+    return (v / np.sqrt((v * v).sum(-1, keepdims=True, dtype=np.float32))).astype(np.float32)
+
+
+def _tangents(n):
+    """Two unit vectors spanning the plane orthogonal to each row of n (float64)."""
+    n = np.asarray(n, np.float64)
+    a = np.eye(3)[np.argmin(np.abs(n), axis=1)]
+    t1 = np.cross(n, a)
+    t1 /= np.linalg.norm(t1, axis=1, keepdims=True)
+    return t1, np.cross(n, t1)
+
+
+def _ref_bsdf(rows):
+    """pyref.bsdf_sample (the reference's BSDF classes, shared transcendentals) of every row of the
+    edge table (16 floats: reference kind, int_ior, ext_ior, albedo rgb, sN, wo, tu, tv, 4 draws)."""
+    from oracle import pyref
+    out = np.zeros((len(rows), 11), np.float32)
+    for i, r in enumerate(rows):
+        out[i] = pyref.bsdf_sample(int(r[0]), r[3:6], r[6:14], r[14:18], float(r[1]), float(r[2]), flavour="rtm")
+    return out
+
+
+def bsdf_edge_rows():
+    """About 20,000 finite BSDF::sample inputs at the edges the 168 generic known answers miss. Per
+    reference kind, 2150 rows that draw each attribute from its families independently:
+      sN     an axis direction | generic with one component of magnitude 1e-20 ... 1e-4 | an axis with
+             its two other components that small | generic (Frame::fromVector's two branches, at and next
+             to their degenerate inputs)
+      wo     sN | -sN | +-sN * (1 + 2^-23) | +-sN * (1 - 2^-23) (|cos| an ulp around 1; not renormalised) |
+             in the tangent plane, lifted by 0, -0.0 or +-1e-8 ... 1e-3 | generic below the surface | generic
+      draws  generic | every slot one of 0, 2^-24, 0.5, 1 - 2^-24
+      albedo 0 | 1 | 4 | generic;  tu, tv one of 0, -0.0, +-0.5, +-1, +-1e5;  (int, ext) one of BSDF_IORS
+    then for glass: wo at the critical angle of each pair with int != ext, on the side where total
+    internal reflection exists, with cos -4 ... +4 ulp around it (exactly, for axis normals, where
+    wol.z is wo's own component; through a float32 normalisation for generic normals), and the deciding
+    draw at R, nextafter(R, +-inf), R being the pdf the reference returns for the draw 0."""
+    rng = np.random.default_rng(20261019)
+    f32 = np.float32
+    axes = np.concatenate([np.eye(3), -np.eye(3)]).astype(f32)
+
+    def tiny(k):
+        return (10.0 ** rng.uniform(-20, -4, k) * rng.choice([-1.0, 1.0], k)).astype(f32)
+
+    def normals(n):
+        out = _unit32(rng.normal(size=(n, 3)))
+        fam = rng.integers(0, 4, n)
+        i0, i1, i2 = (np.flatnonzero(fam == k) for k in range(3))
+        out[i0] = axes[rng.integers(0, 6, len(i0))]
+        out[i1, rng.integers(0, 3, len(i1))] = tiny(len(i1))
+        ax = axes[rng.integers(0, 6, len(i2))].copy()
+        ax[ax == 0] = tiny(2 * len(i2))
+        out[i2] = ax
+        return _unit32(out)
+
+    def outgoing(sn):
+        n = len(sn)
+        out = _unit32(rng.normal(size=(n, 3)))
+        fam = rng.integers(0, 7, n)
+        sign = rng.choice([-1.0, 1.0], (n, 1)).astype(f32)
+        out[fam == 0] = sn[fam == 0]
+        out[fam == 1] = -sn[fam == 1]
+        out[fam == 2] = (sign * sn * f32(1 + 2.0 ** -23))[fam == 2]
+        out[fam == 3] = (sign * sn * f32(1 - 2.0 ** -23))[fam == 3]
+        t1, t2 = _tangents(sn)
+        phi = rng.uniform(0, 2 * np.pi, (n, 1))
+        lift = np.where(rng.random((n, 1)) < 0.4, rng.choice([0.0, -0.0], (n, 1)),
+                        10.0 ** rng.uniform(-8, -3, (n, 1)) * rng.choice([-1.0, 1.0], (n, 1)))
+        out[fam == 4] = _unit32(np.cos(phi) * t1 + np.sin(phi) * t2 + lift * sn.astype(np.float64))[fam == 4]
+        below = (out * sn).sum(1) > 0
+        out[(fam == 5) & below] = -out[(fam == 5) & below]
+        return out
+
+    special = np.array([0.0, 2.0 ** -24, 0.5, 1.0 - 2.0 ** -24], f32)
+    coords = np.array([0.0, -0.0, 0.5, -0.5, 1.0, -1.0, 1e5, -1e5], f32)
+    blocks = []
+    for kind in range(7):
+        n = 2150
+        r = np.zeros((n, 18), f32)
+        r[:, 0] = kind
+        r[:, 1:3] = np.array(BSDF_IORS, f32)[rng.integers(0, len(BSDF_IORS), n)]
+        alb = rng.uniform(0.05, 1, (n, 3)).astype(f32)
+        fam = rng.integers(0, 4, n)
+        for k, v in ((0, 0.0), (1, 1.0), (2, 4.0)):
+            alb[fam == k] = v
+        r[:, 3:6] = alb
+        r[:, 6:9] = normals(n)
+        r[:, 9:12] = outgoing(r[:, 6:9])
+        r[:, 12:14] = coords[rng.integers(0, len(coords), (n, 2))]
+        draws = rng.random((n, 4)).astype(f32)
+        pick = rng.random(n) < 0.5
+        draws[pick] = special[rng.integers(0, 4, (int(pick.sum()), 4))]
+        r[:, 14:18] = draws
+        blocks.append(r)
+    # glass at the critical angle
+    crit = []
+    for ii, ee in BSDF_IORS:
+        if ii == ee:
+            continue
+        side = -1.0 if ii > ee else 1.0  # inside-going (wol.z < 0) when the interior is the denser medium
+        ior = f32(max(ii, ee)) / f32(min(ii, ee))  # fresnelDielectric's iorInt / iorExt on that side
+        cc = f32(np.sqrt(1.0 - 1.0 / (float(ior) * float(ior))))
+        for exact, sns in ((True, np.repeat(axes, 4, axis=0)), (False, _unit32(rng.normal(size=(40, 3))))):
+            t1, t2 = _tangents(sns)
+            phi = rng.uniform(0, 2 * np.pi, (len(sns), 1))
+            phi[::4] = 0.0
+            tan = np.cos(phi) * t1 + np.sin(phi) * t2
+            for off in range(-4, 5):
+                c = cc
+                for _ in range(abs(off)):
+                    c = np.nextafter(c, f32(2.0 if off > 0 else 0.0))
+                wo = np.sqrt(1.0 - float(c) * float(c)) * tan + side * float(c) * sns.astype(np.float64)
+                r = np.zeros((len(sns), 18), f32)
+                r[:, 0], r[:, 1], r[:, 2] = 3, ii, ee
+                r[:, 3:6] = rng.uniform(0.05, 1, (len(sns), 3))
+                r[:, 6:9] = sns
+                r[:, 9:12] = wo.astype(f32) if exact else _unit32(wo)
+                r[:, 12:14] = coords[rng.integers(0, len(coords), (len(sns), 2))]
+                r[:, 14:18] = rng.random((len(sns), 4))
+                crit.append(r)
+    blocks += crit
+    # glass with the deciding draw at R and its two neighbours
+    g = blocks[3].copy()
+    g[:, 14] = 0.0
+    R = _ref_bsdf(g)[:, 6]
+    g = g[(R > 0) & (R < 1)][:1200]
+    R = R[(R > 0) & (R < 1)][:1200]
+    for d0 in (R, np.nextafter(R, f32(2)), np.nextafter(R, f32(-1))):
+        r = g.copy()
+        r[:, 14] = d0
+        blocks.append(r)
+    rows = np.concatenate(blocks).astype(f32)
+    assert np.isfinite(rows).all()
+    return rows
+
+
+def test_bsdf_probe_edge_cases():
+    """bsdf_sample on the device (one rtg_probe_bsdf call) against the reference's own BSDF classes
+    evaluated live (oracle/_ref, shared transcendentals) on bsdf_edge_rows(): all 11 outputs bit for
+    bit, a NaN equal to any NaN. Rows whose reference output holds a NaN stay in the comparison; they
+    are at most 5 % of the rows, so NaN-equals-NaN cannot carry the test. On these inputs the device's
+    smax / smin / fabsf / sqrtf have to behave like the host's std::max / std::min under NaN
+    (fresnelDielectric with |cos| one ulp above 1 takes sqrtf of a negative number, and with cos = 0 and
+    equal iors divides 0 by 0: its clamp turns the NaN into R = 1, so the reference's outputs stay
+    finite there and the device's must too)."""
+    from oracle import pyref
+    if not pyref.available():
+        pytest.fail("oracle/_ref (libref_rtm.so) missing: build it where /root/reference exists")
+    rows = bsdf_edge_rows()
+    assert 19000 <= len(rows) <= 21000 and set(rows[:, 0].astype(int)) == set(range(7))
+    want = _ref_bsdf(rows)
+    nan_rows = np.isnan(want).any(axis=1)
+    print("bsdf edge rows: %d, reference NaN rows: %d, total internal reflections: %d"
+          % (len(rows), nan_rows.sum(), ((rows[:, 0] == 3) & (want[:, 7] == 0)).sum()))
+    assert nan_rows.mean() <= 0.05
+    cases = np.zeros((len(rows), 20), np.float32)
+    cases[:, 0] = [BSDF_KIND_MAP[int(k)] for k in rows[:, 0]]
+    cases[:, 1:18] = rows[:, 1:18]
+    out = np.zeros((len(rows), 11), np.float32)
+    assert N.rtg().rtg_probe_bsdf(N.ptr(cases, C.c_float), len(rows), N.ptr(out, C.c_float)) == 0
+    bad = np.flatnonzero((_nan_canon(out) != _nan_canon(want)).any(axis=1))
+    assert bad.size == 0, "%d rows differ; first: inputs %r device %r reference %r" % (
+        bad.size, rows[bad[0]].tolist(), out[bad[0]].tolist(), want[bad[0]].tolist())
+
+
+def test_texture_probe_matches_golden():
+    """Texture::sample and EnvironmentMap::evaluate as k_shade computes them (rtg_probe_texture runs
+    bilinear<Texels4> and env_eval's body) against the reference's answers recorded in env_tex_kat.npz:
+    cornell-mat's environment map at 2048 uv in [-3, 3]^2 and 2048 directions (the six axes, (0,
+    1.0000001, 0) and (-1, -0.0, 0) among them). Needs no oracle/_ref."""
+    from raytracingrenderer_amd import probe_texture
+    s = loadScene(os.path.join(SCENES, "cornell-mat"), width=64, height=48)
+    assert s.desc.env_texture >= 0
+    tex = s.texture(s.desc.env_texture)
+    g = np.load(os.path.join(GOLD, "env_tex_kat.npz"))
+    assert len(g["uv"]) == 2048 and len(g["dirs"]) == 2048
+    assert_bitexact(probe_texture(tex, g["uv"]), g["tex"], "Texture::sample vs env_tex_kat")
+    assert_bitexact(probe_texture(tex, g["dirs"], env=True), g["env"], "EnvironmentMap::evaluate vs env_tex_kat")
+
+
+def _edge_uv(w, h):
+    """Texture coordinates at the places bilinear()'s rewrites can go wrong: k / size exactly and one
+    ulp either side for k in {0, 1, size - 1, size, size + 1, 3 size} (the wrap, and x + 1 == w), the
+    middle of the last column / row, +-0, denormal and tiny values, 1e5 (|u| * size stays below 2^31,
+    beyond which the reference's float-to-int conversion is undefined), and every one of them negated."""
+    f32 = np.float32
+
+    def axis(n):
+        v = [f32(0.0), f32(1e-45), f32(1e-30), f32(1e5), f32((n - 0.5) / n), f32(0.37)]
+        for k in (0, 1, n - 1, n, n + 1, 3 * n):
+            c = f32(k) / f32(n)
+            v += [c, np.nextafter(c, f32(np.inf)), np.nextafter(c, f32(-np.inf))]
+        v = np.array(v, f32)
+        return np.concatenate([v, -v])
+
+    assert 1e5 * max(w, h) < 2.0 ** 31
+    u, v = axis(w), axis(h)
+    return np.stack(np.meshgrid(u, v, indexing="ij"), -1).reshape(-1, 2).astype(f32)
+
+
+def _edge_dirs(rng):
+    """Directions for EnvironmentMap::evaluate: the axes; both poles and one ulp beyond (acosf gives
+    NaN and std::max(0.0f, NaN) gives 0); z = +-0 on either side of x (u = 0, 0.5); z a denormal or
+    tiny negative with x > 0 (u folds to exactly 1.0 and wraps); 4096 random unit vectors."""
+    f32 = np.float32
+    up = np.nextafter(f32(1), f32(2))
+    d = [(1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1), (0, up, 0), (0, -up, 0),
+         (-1, 0, -0.0), (-1, -0.0, 0.0), (1, 0, -0.0), (-0.6, 0.8, 0.0), (-0.6, 0.8, -0.0), (0.6, -0.8, -0.0),
+         (1, 0, -1e-45), (1, 0, -1e-30), (0.6, 0.8, -1e-10), (1, 0, -1e-8), (-1, 0, -1e-45), (-1, 0, 1e-45),
+         (0.0, 0.5, -0.0), (-0.0, 0.5, 0.0), (-0.0, -0.5, -0.0)]
+    r = rng.normal(size=(4096, 3)).astype(f32)
+    return np.concatenate([np.array(d, f32), _unit32(r)])
+
+
+def test_texture_probe_edge_cases():
+    """The same device arithmetic against the reference's own Texture / EnvironmentMap classes
+    evaluated live (oracle/_ref) on an HDR environment map, a non-square JPEG and a second HDR map,
+    at the coordinates and directions of _edge_uv / _edge_dirs, bit for bit. Then the "uniform
+    texture" short-cut on a constant 3 x 5 texture: the flag on and off give the same bits, and the
+    flag is refused for a texture that is not constant."""
+    from oracle import pyref
+    from raytracingrenderer_amd import NativeError, probe_texture
+    if not pyref.available():
+        pytest.fail("oracle/_ref (libref_rtm.so) missing: build it where /root/reference exists")
+    rng = np.random.default_rng(77)
+    dirs = _edge_dirs(rng)
+    seen = []
+    for scene_dir, pick in ((os.path.join(SCENES, "cornell-mat"), "env"), (staged("bathroom"), "non-square"),
+                            (staged("materialball"), "env")):
+        r = pyref.RefScene(scene_dir, 64, 48, True, flavour="rtm")
+        if pick == "env":
+            ti = r.env_tex
+        else:
+            sizes = [r.texture(i).shape[:2] for i in range(r.ntex)]
+            ti = next(i for i, (th, tw) in enumerate(sizes) if th != tw and th > 1 and tw > 1)
+        assert ti >= 0
+        tex = r.texture(ti)
+        h, w = tex.shape[:2]
+        seen.append((w, h))
+        uv = np.concatenate([_edge_uv(w, h), rng.uniform(-3, 3, (2048, 2)).astype(np.float32)])
+        what = "%s texture %d (%dx%d)" % (os.path.basename(scene_dir), ti, w, h)
+        assert_bitexact(_nan_canon(probe_texture(tex, uv)).view(np.float32),
+                        _nan_canon(r.tex_sample(ti, uv)).view(np.float32), "Texture::sample, " + what)
+        assert_bitexact(_nan_canon(probe_texture(tex, dirs, env=True)).view(np.float32),
+                        _nan_canon(r.env_eval(ti, dirs)).view(np.float32), "EnvironmentMap::evaluate, " + what)
+    assert any(w != h for w, h in seen) and len(set(seen)) == 3, seen
+    const = np.empty((5, 3, 3), np.float32)
+    const[:] = np.float32([0.3, 1.7, 0.05])
+    uv = np.concatenate([_edge_uv(3, 5), rng.uniform(-3, 3, (512, 2)).astype(np.float32)])
+    for coords, env in ((uv, False), (dirs, True)):
+        assert_bitexact(probe_texture(const, coords, env=env, uniform=True), probe_texture(const, coords, env=env),
+                        "uniform short-cut, env=%s" % env)
+    const[4, 2, 1] = np.float32(1.75)
+    with pytest.raises(NativeError):
+        probe_texture(const, uv, uniform=True)
+
+
 def test_c3_full_size_64spp_sampled_pixels():
     """The bench workload itself (C3: 1M triangles, 1024^2, 64 spp in one wavefront chunk with the
     pixel-major two-pass fold): 1500 random pixels' film values equal the oracle's 64 per-path

@@ -185,6 +185,37 @@ def test_oracle_film_equals_reference_classes(case, flavour):
     assert rc.tolist() == oc[:3].tolist()
 
 
+@pytest.mark.parametrize("case", [3, 6])
+def test_oracle_equals_reference_classes_at_the_table_limits(case, tmp_path):
+    """The scenes of tests/test_shade_tables.py with 64 materials / 48 lights and with about 150
+    materials / 281 lights (environment light included; every fixture scene has at most 6 lights): the C
+    oracle's path tracer, light tracer and instant radiosity against the same integrators on RTBase's own
+    compiled classes (oracle/_ref, shared transcendentals), bit for bit. The GPU is compared with the
+    oracle on these scenes; this pins the oracle itself there, light selection included."""
+    from oracle import pyref
+    from shade_scenes import table_cases, table_counts, write_table_scene
+    if not pyref.available():
+        pytest.skip("oracle/_ref not built")
+    n_emitters, n_extra, envmap, want_mats, want_lights, _ = table_cases()[case]
+    path = write_table_scene(tmp_path / "scene", n_emitters, n_extra, envmap)
+    s = loadScene(path)
+    assert table_counts(s) == (want_mats, want_lights)
+    r = pyref.RefScene(path, 64, 48, False, flavour="rtm")
+    assert r.nlight == want_lights
+    o = Oracle(s, 6, "rtm")
+    a, ca = r.render(3, seed=31, max_depth=6, threads=8)
+    b, cb = o.render(3, seed=31, threads=8, count=True)
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), (a != b).sum()
+    assert ca.tolist() == cb[:3].tolist()
+    assert np.isfinite(b).all() and (b != 0).mean() > 0.5
+    a, b = pyref.render_light(r, 1, seed=33), o.render_light(1, seed=33)
+    assert (b != 0).sum() > 100
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), (a != b).sum()
+    a, b = pyref.render_instant_radiosity(r, 1, seed=34, n_vpl=8), o.render_instant_radiosity(1, seed=34, n_vpl=8)
+    assert (b != 0).sum() > 100
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), (a != b).sum()
+
+
 @pytest.mark.host_glibc
 def test_c1_known_answer_from_reference_classes():
     """SURVEY.md §8c's C1 md5 (the reference integrator built in the survey, glibc) is reproduced by

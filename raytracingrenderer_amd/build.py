@@ -28,15 +28,17 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("RTG_ARCH", "gfx950")
 
 HOST_SRC = ["host/image_io.cpp", "host/jpeg_decode.cpp", "host/gem_json.cpp", "host/scene_front.cpp"]
-DEVICE_SRC = ["device/rtg_kernels.hip", "device/rtg_shade.hip", "device/rtg_light.hip", "device/rtg_multi.hip",
-              "device/rtg_bvh.hip", "device/rtg_denoise.hip"]
+DEVICE_SRC = ["device/rtg_trace.hip", "device/rtg_scene.hip", "device/rtg_render.hip", "device/rtg_api.hip",
+              "device/rtg_shade.hip", "device/rtg_light.hip", "device/rtg_multi.hip", "device/rtg_bvh.hip",
+              "device/rtg_denoise.hip"]
 # per-unit compile flags: k_shade's translation unit takes LLVM's max-ilp scheduler, which its
 # latency-bound body prefers, while the traversal keeps the default; the traversal's
 # unit is built without SLP vectorisation, whose packed FP32 pairs in the triangle test held k_trace at
 # 80 VGPRs (6 waves per SIMD); without them it needs 64 and runs at 7 (C3 +4 %). k_shade
-# without it too: 62 instead of 68 VGPRs, fewer pair moves (C5 shading -4 %)
-DEVICE_FLAGS = {"device/rtg_shade.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-fno-slp-vectorize"],
-                "device/rtg_kernels.hip": ["-fno-slp-vectorize"]}
+# without it too: 62 instead of 68 VGPRs, fewer pair moves (C5 shading -4 %). The units split off the
+# traversal's keep its flag: their kernels and rtg_scene.hip's host arithmetic were compiled with it.
+DEVICE_FLAGS = {"device/rtg_shade.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-fno-slp-vectorize"]}
+DEVICE_FLAGS.update({"device/rtg_%s.hip" % u: ["-fno-slp-vectorize"] for u in ("trace", "scene", "render", "api")})
 
 
 def _newer(out, deps):
@@ -116,49 +118,19 @@ def build_host(force=False):
     return out
 
 
-def build_device(force=False, debug=False):
-    d = os.path.join(LIB, "debug") if debug else LIB
-    os.makedirs(d, exist_ok=True)
-    out = os.path.join(d, "librtg.so")
-    src = [os.path.join(CSRC, s) for s in DEVICE_SRC]
-    if force or _stale(out, "device", "rtg-build-id:", debug):
-        bid = source_hash("device", debug)
-        # one object per unit (each with its own flags, compiled in parallel), then one link
-        with tempfile.TemporaryDirectory() as tmp:
-            objs, procs = [], []
-            for rel, path in zip(DEVICE_SRC, src):
-                obj = os.path.join(tmp, os.path.basename(rel) + ".o")
-                cmd = ([HIPCC, "--offload-arch=" + ARCH] + DEVICE_CXXFLAGS + ['-DRTG_BUILD_ID="%s"' % bid] +
-                       (["-DRTG_DEBUG=1"] if debug else []) + DEVICE_FLAGS.get(rel, []) + ["-c", "-o", obj, path])
-                procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
-                objs.append(obj)
-            for cmd, pr in procs:
-                log = pr.communicate()[0]
-                if pr.returncode != 0:
-                    sys.stderr.write(log)
-                    raise RuntimeError("build failed: " + " ".join(cmd))
-            _run([HIPCC, "--offload-arch=" + ARCH, "-fPIC", "-shared", "-o", out] + objs + DEVICE_LDFLAGS)
-    return out
-
-
-def build_variant(name, extra_flags):
-    """A/B variant of librtg (tools/mkab.sh): the product's units and flags plus `extra_flags`
-    (e.g. -DRTG_FOO=1), into lib/ab/<name>.so; loaded through RTG_LIB by tools/ab*.sh. A flag written
-    `unit:flag` (e.g. `rtg_kernels:-fslp-vectorize`) goes to that unit only; extra flags come after the
-    product's, so they override them."""
-    d = os.path.join(LIB, "ab")
-    os.makedirs(d, exist_ok=True)
-    out = os.path.join(d, name + ".so")
-    src = [os.path.join(CSRC, s) for s in DEVICE_SRC]
+def _compile_and_link(out, build_id, extra_flags=()):
+    """librtg from DEVICE_SRC into `out`: one object per unit (each with its own DEVICE_FLAGS, compiled
+    in parallel), then one link. An extra flag written `unit:flag` goes to that unit only; extra flags
+    come after the product's, so they override them."""
     with tempfile.TemporaryDirectory() as tmp:
         objs, procs = [], []
-        for rel, path in zip(DEVICE_SRC, src):
+        for rel in DEVICE_SRC:
             obj = os.path.join(tmp, os.path.basename(rel) + ".o")
             unit = os.path.splitext(os.path.basename(rel))[0]
             flags = [f.split(":", 1)[1] if ":" in f else f for f in extra_flags
                      if ":" not in f or f.split(":", 1)[0] == unit]
-            cmd = ([HIPCC, "--offload-arch=" + ARCH] + DEVICE_CXXFLAGS + ['-DRTG_BUILD_ID="ab-%s"' % name] +
-                   DEVICE_FLAGS.get(rel, []) + flags + ["-c", "-o", obj, path])
+            cmd = ([HIPCC, "--offload-arch=" + ARCH] + DEVICE_CXXFLAGS + ['-DRTG_BUILD_ID="%s"' % build_id] +
+                   DEVICE_FLAGS.get(rel, []) + flags + ["-c", "-o", obj, os.path.join(CSRC, rel)])
             procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
             objs.append(obj)
         for cmd, pr in procs:
@@ -168,6 +140,23 @@ def build_variant(name, extra_flags):
                 raise RuntimeError("build failed: " + " ".join(cmd))
         _run([HIPCC, "--offload-arch=" + ARCH, "-fPIC", "-shared", "-o", out] + objs + DEVICE_LDFLAGS)
     return out
+
+
+def build_device(force=False, debug=False):
+    d = os.path.join(LIB, "debug") if debug else LIB
+    os.makedirs(d, exist_ok=True)
+    out = os.path.join(d, "librtg.so")
+    if force or _stale(out, "device", "rtg-build-id:", debug):
+        _compile_and_link(out, source_hash("device", debug), ["-DRTG_DEBUG=1"] if debug else [])
+    return out
+
+
+def build_variant(name, extra_flags):
+    """A/B variant of librtg (tools/mkab.sh): the product's units and flags plus `extra_flags`
+    (e.g. -DRTG_FOO=1, or `rtg_trace:-fslp-vectorize` for one unit), into lib/ab/<name>.so; loaded
+    through RTG_LIB by tools/ab*.sh."""
+    os.makedirs(os.path.join(LIB, "ab"), exist_ok=True)
+    return _compile_and_link(os.path.join(LIB, "ab", name + ".so"), "ab-" + name, extra_flags)
 
 
 def build_cli(force=False):
@@ -229,18 +218,28 @@ def build_sanitized(force=False):
     return out
 
 
-def build_sbvh_check(force=False):
-    """Test infrastructure: tests/native/sbvh_check (rtg_bvh.hip's host code + librth, no GPU code
-    run) into tests/native/_build/; tests/test_bvh.py runs it."""
+def _build_test_program(name, extra_src, libs, force):
+    """Test infrastructure: tests/native/<name>.cpp (+ extra_src), linked with `libs` of lib/, into
+    tests/native/_build/<name>. CPU programs: no GPU code is run."""
     nat = os.path.join(ROOT, "tests", "native")
-    out_dir = os.path.join(nat, "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    out = os.path.join(out_dir, "sbvh_check")
-    src = [os.path.join(nat, "sbvh_check.cpp"), os.path.join(CSRC, "device", "rtg_bvh.hip")]
-    if force or _newer(out, _deps(src) + [os.path.join(LIB, "librth.so")]):
+    os.makedirs(os.path.join(nat, "_build"), exist_ok=True)
+    out = os.path.join(nat, "_build", name)
+    src = [os.path.join(nat, name + ".cpp")] + extra_src
+    if force or _newer(out, _deps(src) + [os.path.join(LIB, "lib%s.so" % l) for l in libs]):
         _run([HIPCC, "-O2", "-std=c++17", "-ffp-contract=off", "-o", out] + src +
-             ["-L" + LIB, "-lrth", "-Wl,-rpath," + LIB])
+             ["-L" + LIB] + ["-l" + l for l in libs] + ["-Wl,-rpath," + LIB])
     return out
+
+
+def build_sbvh_check(force=False):
+    """rtg_bvh.hip's host code + librth: the own tree's spatial splits; tests/test_bvh.py runs it."""
+    return _build_test_program("sbvh_check", [os.path.join(CSRC, "device", "rtg_bvh.hip")], ["rth"], force)
+
+
+def build_scene_digest(force=False):
+    """librtg's prepare_scene on a loaded scene, one digest per device record array;
+    tests/test_scene_digest.py runs it."""
+    return _build_test_program("scene_digest", [], ["rth", "rtg"], force)
 
 
 def build_ref(force=False):

@@ -335,8 +335,8 @@ struct Builder {
 
 }  // namespace
 
-// The own binary tree with spatial splits over the scene's triangles (rtg_kernels.hip calls it for
-// prepare_scene when RTG_SBVH is set). The top levels are built first, down to a depth that leaves
+// The own binary tree with spatial splits over the scene's triangles (rtg_scene.hip's prepare_scene
+// calls it). The top levels are built first, down to a depth that leaves
 // about 4 subtrees per host thread; the subtrees are then built on threads, each with a share of the
 // duplication budget proportional to its references (so the tree does not depend on thread timing),
 // and stitched in (a subtree's root takes its placeholder's id; children keep larger ids than their

@@ -156,11 +156,12 @@ struct SceneView {
     int usew;            // wide tree available (finite bounds, children inside parents)
     float root_box[6];   // bounds of the reference root node
     float cull_scale;    // scene magnitude used for the conservative cull inflation
-    // small scenes (the wide nodes, triangle records and leaf boxes fit RTG_SMALL_F4 float4s, e.g.
-    // the cornell box of config C2): one image [wide nodes | triangles | leaf boxes] that k_trace
-    // copies into LDS per block, so every record fetch of the walk is an LDS read
+    // small scenes (the wide nodes and triangle records fit RTG_SMALL_F4 float4s, e.g. the cornell
+    // box of config C2): one image [wide nodes | triangles] that k_trace copies into LDS per block,
+    // so every node and triangle fetch of the walk is an LDS read (leaf boxes: global memory)
     const float4* img;   // null: the walk reads global memory
-    int img_n4, img_tri, img_lb;  // image size and the float4 offsets of the triangles / leaf boxes
+    int img_n4, img_tri;  // image size and the float4 offset of the triangles
+    int img_lb;           // the image's end; no kernel reads it (kept: the kernel-argument layout)
 };
 
 // ------------------------------------------------------------------ Texture::sample

@@ -1,7 +1,7 @@
 // rtg_internal.h — declarations shared by the translation units of librtg.so (not part of the ABI):
 // launch parameters of the wavefront kernels, the handle, and the host helpers that launch the
-// traversal for the other integrators (rtg_kernels.hip: path tracer + traversal; rtg_light.hip:
-// light tracing and instant radiosity, Renderer.h:82-326).
+// traversal for the other integrators (rtg_render.hip: path tracer; rtg_trace.hip: traversal;
+// rtg_light.hip: light tracing and instant radiosity, Renderer.h:82-326).
 #pragma once
 #include "rtg_dev.h"
 #include "../../../include/rtg.h"
@@ -35,12 +35,6 @@ using namespace rtgd;
 #define RTG_SMALL_F4 192    // small-scene image limit, float4s (3 KB; cornell's SBVH image is 188): with
 #endif                      // 7 x 256 B of stack a one-wave block takes 4.9 KB, 28 blocks (7 waves) per CU
                             // (224 float4s and 11 entries: 6.5 KB, 6 waves; C2 walk -7 %)
-#ifndef RTG_SMALL_LB
-#define RTG_SMALL_LB 0      // 1: the small-scene image holds the leaf boxes too; 0: they stay in global
-#endif                      // memory, read once per candidate hit (C2 +4.8 %: cornell's SBVH image then fits)
-#ifndef RTG_CAM_GRID
-#define RTG_CAM_GRID 1      // the camera launch runs at most one one-wave block per 64 rays (its one
-#endif                      // work counter then takes no probes from waves without work; +0.5 %)
 #ifndef RTG_POSTPONE
 #define RTG_POSTPONE 32     // park a reached leaf and keep walking; run the leaves of a wave together
                             // once this many lanes hold one (or no lane can walk on, or the queue is dry)
@@ -50,9 +44,6 @@ using namespace rtgd;
                             // C5's 32-spp step in one chunk, +3 % once allocated, but allocations past
                             // ~half the VRAM take seconds: a one-shot C5 frame 4.8 -> 8.4 s)
 #endif
-#ifndef RTG_PEND2
-#define RTG_PEND2 1         // a lane parks a second reached leaf instead of idling until the leaf phase
-#endif                      // (node-step lane use 0.70 -> 0.77 on C3: +1 to +2 %)
 #ifndef RTG_REFILL
 #define RTG_REFILL 12       // refill idle lanes once at least this many are idle (the setup code then
                             // runs with more lanes per execution)
@@ -85,12 +76,6 @@ using namespace rtgd;
 #endif
 #ifndef RTG_SAH_BINS
 #define RTG_SAH_BINS 128    // centroid bins per axis of the binned SAH (64: C5 -2.3 %)
-#endif
-#ifndef RTG_SBVH
-#define RTG_SBVH 1          // spatial splits (rtg_bvh.hip build_sbvh); 0: object splits only
-#endif
-#ifndef RTG_UNIFORM_TEX
-#define RTG_UNIFORM_TEX 1   // constant textures of any size take the 1x1 path (no texel fetches)
 #endif
 #ifndef RTG_SBVH_BINS
 #define RTG_SBVH_BINS 32    // slabs per axis of a spatial split
@@ -233,8 +218,6 @@ static __device__ __forceinline__ unsigned prefix_lt(unsigned long long m) {
     return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
 
-
-
 // ------------------------------------------------------------------ host side
 extern thread_local std::string g_err;
 
@@ -247,8 +230,6 @@ struct RoctxRange {
     RoctxRange(const RoctxRange&) = delete;
     RoctxRange& operator=(const RoctxRange&) = delete;
 };
-// "rtg:trace b=<b>" / "rtg:shade b=<b>" names for b < 32 (static strings: roctx copies nothing)
-const char* roctx_stage_name(int kind, int b);
 
 #define HIPOK(expr)                                                                          \
     do {                                                                                     \
@@ -266,8 +247,6 @@ const char* roctx_stage_name(int kind, int b);
             return RTG_ERR_HIP;                                                              \
         }                                                                                    \
     } while (0)
-
-
 
 template <class T>
 static int dev_upload(T** dst, const std::vector<T>& src) {
@@ -321,7 +300,8 @@ struct rtg_handle {
     uint32_t max_paths = 1u << 30;  // 1G paths in flight at most; the chunk is held to half the free HBM
     size_t mem_cap = 0;  // != 0: path-state budget of this handle (a group rehearsing k ranks on one
                          // device gives each 1/k of half the device's free HBM, so their chunks match)
-    int n_cu = 256, trace_blocks = 0, trace_blocks_count = 0, trace_blocks_small = 0, trace_blocks_small_count = 0;
+    int n_cu = 256;
+    int trace_blocks[2][2] = {};  // [COUNT][SMALL]: the resident grid of each k_trace variant (size_trace_grids)
     int wavetime = 0;  // RTG_DEBUG builds: per-wave clocks of the first chunk (RTG_OPT_WAVETIME)
     int capture_launch = -1;  // RTG_DEBUG builds: trace launch of chunk 0 whose fetches are captured
     uint4* d_cap = nullptr;           // its chains (TraceIO::cap)
@@ -385,15 +365,14 @@ struct rtg_handle {
 };
 #define RTG_CNT_PENDING 0xFFFFFFFFu
 
-
 // The device records of a scene, built on the host from an rtg_scene_desc (prepare_scene) and
 // uploaded per device (upload_scene); rtg_create does both, a group prepares once.
 struct HostScene {
     std::vector<DevNode> nodes;
     std::vector<DevNodeQ> nodesq;
     std::vector<float4> leafbox;
-    std::vector<float4> img;   // small scenes: [wide nodes | triangles | leaf boxes] (SceneView::img)
-    int img_tri = 0, img_lb = 0;
+    std::vector<float4> img;   // small scenes: [wide nodes | triangles] (SceneView::img)
+    int img_tri = 0, img_lb = 0;  // (img_lb: see SceneView)
     std::vector<DevTri48> tris48;
     std::vector<DevShade> shade;
     std::vector<DevMat> mats;
@@ -414,9 +393,22 @@ struct HostScene {
 
 // rtg_bvh.hip: the own binary tree with spatial splits over the triangles (descriptor node format)
 bool build_sbvh(const rtg_scene_desc* d, std::vector<int32_t>& lk, std::vector<float>& bd);
-// rtg_kernels.hip
+// rtg_scene.hip
 int prepare_scene(const rtg_scene_desc* d, HostScene& hs);
+// rtg_api.hip
 int upload_scene(int device, const HostScene& hs, rtg_handle* h);
+// rtg_trace.hip: the grid sizes of the k_trace variants from their occupancy (upload_scene)
+int size_trace_grids(rtg_handle* h);
+static inline int trace_blocks_max(const rtg_handle* h) {
+    return std::max({h->trace_blocks[0][0], h->trace_blocks[0][1], h->trace_blocks[1][0], h->trace_blocks[1][1]});
+}
+// RTG_DEBUG builds: capture buffers and slice table for the launch `io` describes (render_impl)
+int capture_begin(rtg_handle* h, TraceIO& io, unsigned seg_tiles, hipStream_t ss);
+// one k_trace launch (closest-hit rays of io.queue and any-hit rays of io.squeue) on stream st
+// (max_blocks != 0: at most that many one-wave blocks instead of the resident grid)
+int launch_trace(rtg_handle* h, const TraceIO& io, hipStream_t st, unsigned max_blocks = 0);
+// rtg_render.hip
+void free_chunk(ChunkSlot& sl);
 int ensure_ovf(rtg_handle* h, ChunkSlot& sl);
 int set_pixels(rtg_handle* h, const uint32_t* tiles, uint32_t n_tiles);
 // path state of P paths with maxb contribution planes in slot sl (+ the id queues q[0..1] if asked)
@@ -432,9 +424,6 @@ int flush_pending(rtg_handle* h);
 int join_frames(rtg_handle* h);
 // k_generate for the paths of a (camera rays at pixel centres, Scene.h:43-54)
 int launch_generate(rtg_handle* h, const ChunkArgs& a, const PathBufs& pb, hipStream_t st);
-// one k_trace launch (closest-hit rays of io.queue and any-hit rays of io.squeue) on stream st
-// (max_blocks != 0: at most that many one-wave blocks instead of the resident grid)
-int launch_trace(rtg_handle* h, const TraceIO& io, hipStream_t st, unsigned max_blocks = 0);
 // rtg_denoise.hip: filter d_sum / spp (a film on h's device) with h's guides into h's result buffer,
 // and into `out` (host) when given; waits for the result
 int denoise_film(rtg_handle* h, const float* d_sum, uint32_t spp, const rtg_denoise_params* p, float* out);

@@ -1,5 +1,5 @@
 // rtg_light.hip — the reference's two light-path integrators on the wavefront machinery of
-// rtg_kernels.hip (k_trace for every ray query):
+// rtg_trace.hip and rtg_render.hip (k_trace for every ray query):
 //
 //   rtg_render_light               RayTracer::lightTracer / lightTrace_init / lightTracePath /
 //                                  connectToCamera (RTBase/Renderer.h:221-326)

@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256) void k_film_scatter(const float* __restrict__ 
     film[3 * (size_t)p + 2] = src[3 * (size_t)i + 2];
 }
 
-// the pixel order of set_pixels (rtg_kernels.hip): tile by tile, row-major inside a tile
+// the pixel order of set_pixels (rtg_render.hip): tile by tile, row-major inside a tile
 static void tile_pixels(uint32_t W, uint32_t H, const uint32_t* tiles, uint32_t n_tiles, std::vector<uint32_t>& out) {
     const uint32_t tx = (W + 31) / 32;
     for (uint32_t i = 0; i < n_tiles; ++i) {

@@ -1,4 +1,4 @@
-// rtg_shade.hip — k_shade, the shading stage of the wavefront path tracer (see rtg_kernels.hip's
+// rtg_shade.hip — k_shade, the shading stage of the wavefront path tracer (see rtg_render.hip's
 // header for the bounce loop), in a translation unit of its own so that it can be compiled with its
 // own instruction-scheduling strategy (raytracingrenderer_amd/build.py: SHADE_FLAGS).
 #include "rtg_internal.h"

@@ -197,6 +197,23 @@ def rtm_digest_fixture(stride=127):
               open(os.path.join(GOLD, "rtm_digest.json"), "w"), indent=1, sort_keys=True)
 
 
+def device_digest_fixture():
+    """The device records prepare_scene builds (tests/native/scene_digest, linked with this tree's
+    librth / librtg) for the inputs of tests/test_scene_digest.py -> device_scene_digests.json.
+    Regenerate only for an intended change of the records: the committed values were recorded from
+    the tree before rtg_kernels.hip was split, and a refactor must reproduce them."""
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from raytracingrenderer_amd import build
+    from test_scene_digest import INPUTS, run_digest
+    build.build_host()
+    build.build_device()
+    exe = build.build_scene_digest()
+    with tempfile.TemporaryDirectory() as tmp:
+        out = {name: run_digest(exe, name, tmp) for name in INPUTS}
+    json.dump(out, open(os.path.join(GOLD, "device_scene_digests.json"), "w"), indent=1, sort_keys=True)
+
+
 def tonemap_fixture():
     """Film::tonemap (Imaging.h:233-242) of the reference's own Film class on a random film with
     negative, zero, tiny, saturating and non-finite values, at two exposures -> tonemap_kat.npz."""
@@ -326,5 +343,7 @@ if __name__ == "__main__":
         add_scene_digests(["materialball_f"])
     elif "--tonemap" in sys.argv:
         tonemap_fixture()
+    elif "--device-digests" in sys.argv:
+        device_digest_fixture()
     else:
         main()

@@ -19,7 +19,7 @@ def kernels():
         pytest.skip("hipcc not available")
     from raytracingrenderer_amd.build import DEVICE_FLAGS  # each unit with the flags the build uses
     res = {"_asm": {}}
-    for rel in ("device/rtg_kernels.hip", "device/rtg_shade.hip"):
+    for rel in ("device/rtg_trace.hip", "device/rtg_shade.hip"):
         with tempfile.TemporaryDirectory() as d:
             out = os.path.join(d, "k.s")
             subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"] +

@@ -38,7 +38,8 @@ extern "C" {
  *    which rtg_group_reduce now uses in place of a whole-film ncclReduce; rtg_stats.chunk_samples
  * 6: rtg_group_render_async / rtg_group_reduce_async / rtg_group_synchronize (queued group frames);
  *    rtg_film_scatter takes the film's pixel count; rtg_stats.lane_idle_* appended
- *    (additive, still 6: the denoiser, rtg_denoise_* and rtg_group_denoise) */
+ *    (additive, still 6: the denoiser, rtg_denoise_* and rtg_group_denoise; camera sampling,
+ *    rtg_*_camera_sampling and rtg_probe_camera_samples) */
 #define RTG_ABI_VERSION 6
 
 /* error codes */
@@ -130,6 +131,7 @@ typedef struct rtg_stats {
                                    /* pixel centre's for every sample (Renderer.h:805-808), so a chunk  */
                                    /* traces one per pixel and its samples share the first hit;         */
                                    /* extension_rays counts one per sample, as the reference casts them */
+                                   /* (rtg_set_camera_sampling with a filter or a lens: one per path)   */
     uint64_t chunk_samples;        /* samples per pixel of the largest wavefront chunk issued since the */
                                    /* last rtg_clear (ABI 5): the chunk shape of the render           */
     /* RTG_OPT_COUNT (ABI 6): lanes not stepping a node in a traversal loop iteration, by reason,   */
@@ -186,6 +188,53 @@ int  rtg_set_options(rtg_handle* h, int max_depth, int flags, uint32_t max_paths
 #define RTG_INTEGRATOR_NORMALS    3
 #define RTG_INTEGRATOR_DIRECT_MIS 4
 int  rtg_set_integrator(rtg_handle* h, int integrator);
+
+/* ---- camera sampling: pixel-filter jitter and a thin-lens aperture (DESIGN.md "Camera sampling").
+ * renderTile sends every sample of a pixel through the pixel centre of a pinhole camera; that is
+ * the default here (RTG_FILTER_NONE, lens_radius 0), with one camera ray traced per pixel and
+ * shared by its samples. With a filter or a lens, every sample gets a camera ray of its own.
+ * Filter importance sampling: sample s of pixel (x, y) crosses the film at
+ * (x + 0.5 + dx, y + 0.5 + dy), the offset drawn from the filter's own density, and is added with
+ * weight 1 to pixel (x, y) alone (no splat to neighbours), so the sample-order fold, chunking, tiles
+ * and queued frames stay invisible in the film's bits. The draws come from a PCG32 stream of their
+ * own, pcg_seed(seed ^ 0x9E3779B97F4A7C15, pcg_inc(pixel, sample)), four in order and always all
+ * four: u0 (x), u1 (y), u2, u3 (lens); the path's own stream draws what it draws without them.
+ * IEEE float32 in the order written, no contraction:
+ *   RTG_FILTER_BOX   d = (u * 2.0f - 1.0f) * r                                   (default r 0.5)
+ *   RTG_FILTER_TENT  t = u < 0.5f ? sqrtf(2.0f * u) - 1.0f : 1.0f - sqrtf(2.0f - 2.0f * u),
+ *                    d = t * r                                                   (r 1 is the usual tent)
+ *   px = ((float)x + 0.5f) + dx, py likewise; Camera::generateRay's arithmetic on (px, py) gives the
+ *   normalised direction d from the origin o.
+ * filter_radius must be finite and in [0, RTG_FILTER_MAX_RADIUS]. (No Gaussian: sampling it needs
+ * logf or an inverse erf, which include/rtg_math.h does not restate.)
+ * Thin lens, lens_radius R >= 0 (finite; 0 = pinhole), focal_distance f finite and > 0 whenever
+ * R > 0. With xc, yc, zc the first three columns of camera.m and dot(a, b) = (ax bx + ay by) + az bz:
+ *   ft = f / fabsf(dot(d, zc));  P = o + d * ft  (component-wise)            the point in focus
+ *   rr = R * sqrtf(u2);  (s, c) = sincosf(6.2831855f * u3)                   include/rtg_math.h's
+ *   o' = (o + xc * (rr * c)) + yc * (rr * s);  d' = (P - o') * (1.0f / sqrtf(|P - o'|^2))
+ * The setting applies to rtg_render, rtg_render_async, rtg_render_adaptive and the group calls, for
+ * every integrator of rtg_set_integrator. It does not apply to rtg_render_light (no camera rays), to
+ * rtg_render_instant_radiosity's camera pass, or to the denoiser's guides (one centre / pinhole
+ * sample each: rtg_denoise saves and restores the setting, as it does the integrator).
+ * rtg_set_camera_sampling first issues and waits for queued frames; an argument error leaves the
+ * previous setting in place. In per-sample mode rtg_stats.traced_camera_rays counts one ray per
+ * path, and rtg_launch_rays' launch 0 is the chunk's paths. */
+#define RTG_FILTER_NONE 0
+#define RTG_FILTER_BOX  1
+#define RTG_FILTER_TENT 2
+#define RTG_FILTER_MAX_RADIUS 4.0f
+typedef struct rtg_camera_sampling {
+    int32_t filter;                /* RTG_FILTER_* */
+    float filter_radius, lens_radius, focal_distance;
+} rtg_camera_sampling;
+int  rtg_camera_sampling_defaults(rtg_camera_sampling* p);  /* NONE, 0.5f, 0, 1 */
+int  rtg_set_camera_sampling(rtg_handle* h, const rtg_camera_sampling* p);
+int  rtg_get_camera_sampling(rtg_handle* h, rtg_camera_sampling* p);
+/* The generate kernel's own function on n (pixel, sample) pairs under the handle's setting: rays
+ * n*8 (o.xyz, 0, d.xyz, 0: the layout rtg_trace_closest takes), film_xy n*2 (px, py) or NULL.
+ * A pixel >= width*height or a sample >= RTG_MAX_SAMPLES_PER_KEY: RTG_ERR_ARG. */
+int  rtg_probe_camera_samples(rtg_handle* h, const uint32_t* pixels, const uint32_t* samples, uint32_t n,
+                              uint64_t seed, float* rays, float* film_xy);
 
 /* Add samples [first_sample, first_sample+n_samples) of every pixel in the listed 32x32 tiles
  * (tile id = ty*tilesX + tx, RTBase TILE_SIZE=32; tile_ids=NULL = all tiles) to the film, in
@@ -275,6 +324,7 @@ void rtg_group_destroy(rtg_group* g);
 int  rtg_group_size(rtg_group* g);
 rtg_handle* rtg_group_handle(rtg_group* g, int rank);  /* e.g. for rtg_get_stats; owned by the group */
 int  rtg_group_set_options(rtg_group* g, int max_depth, int flags, uint32_t max_paths);
+int  rtg_group_set_camera_sampling(rtg_group* g, const rtg_camera_sampling* p);  /* every rank's handle */
 int  rtg_group_render(rtg_group* g, uint32_t first_sample, uint32_t n_samples, uint64_t seed);
 int  rtg_group_reduce(rtg_group* g);  /* the films stay per device; the assembled film goes to a separate buffer */
 /* Queued forms (the frame loop of Main.cpp:74-118 on N devices). rtg_group_render_async is every
@@ -322,7 +372,8 @@ int  rtg_get_stats(rtg_handle* h, rtg_stats* out);
  * order (chunk by chunk, bounce by bounce): n receives the count, at most max are written. */
 int  rtg_launch_times(rtg_handle* h, double* trace_ms, uint32_t max, uint32_t* n);
 /* The rays each trace launch of the last timed render's last chunk walked (path tracer: launch b =
- * bounce b's extension rays + bounce b-1's shadow rays; launch 0 the camera rays, one per pixel). */
+ * bounce b's extension rays + bounce b-1's shadow rays; launch 0 the camera rays, one per pixel, or
+ * one per path under rtg_set_camera_sampling with a filter or a lens). */
 int  rtg_launch_rays(rtg_handle* h, uint64_t* rays, uint32_t max, uint32_t* n);
 /* Diagnostics of the locality-matched roofline (builds with RTG_DEBUG=1 only; RTG_ERR_ARG
  * otherwise). rtg_debug_capture(h, b): the next render records every record fetch of trace launch

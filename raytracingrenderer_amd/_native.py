@@ -15,6 +15,8 @@ RTG_OPT_NO_COALESCE = 64
 RTG_INTEGRATOR_PATH, RTG_INTEGRATOR_DIRECT, RTG_INTEGRATOR_ALBEDO, RTG_INTEGRATOR_NORMALS = 0, 1, 2, 3
 RTG_INTEGRATOR_DIRECT_MIS = 4
 RTG_PROBE_TEX_SAMPLE, RTG_PROBE_TEX_ENV, RTG_PROBE_TEX_UNIFORM = 0, 1, 2
+RTG_FILTER_NONE, RTG_FILTER_BOX, RTG_FILTER_TENT = 0, 1, 2
+RTG_FILTER_MAX_RADIUS = 4.0
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
@@ -66,6 +68,11 @@ class rtg_stats(C.Structure):
 class rtg_denoise_params(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("normal_squarings", C.c_uint32), ("sigma_colour", C.c_float),
                 ("sigma_albedo", C.c_float)]
+
+
+class rtg_camera_sampling(C.Structure):
+    _fields_ = [("filter", C.c_int32), ("filter_radius", C.c_float), ("lens_radius", C.c_float),
+                ("focal_distance", C.c_float)]
 
 
 class rth_load_options(C.Structure):
@@ -141,6 +148,12 @@ RTG_EXPORTS = [
     ("rtg_denoise_copy_device", C.c_int, [C.c_void_p, C.c_void_p]),
     ("rtg_denoise_ms", C.c_double, [C.c_void_p]),
     ("rtg_group_denoise", C.c_int, [C.c_void_p, C.POINTER(rtg_denoise_params), f32p]),
+    # camera sampling: pixel-filter jitter and a thin-lens aperture (rtg_render.hip)
+    ("rtg_camera_sampling_defaults", C.c_int, [C.POINTER(rtg_camera_sampling)]),
+    ("rtg_set_camera_sampling", C.c_int, [C.c_void_p, C.POINTER(rtg_camera_sampling)]),
+    ("rtg_get_camera_sampling", C.c_int, [C.c_void_p, C.POINTER(rtg_camera_sampling)]),
+    ("rtg_group_set_camera_sampling", C.c_int, [C.c_void_p, C.POINTER(rtg_camera_sampling)]),
+    ("rtg_probe_camera_samples", C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32, C.c_uint64, f32p, f32p]),
 ]
 
 RTH_EXPORTS = [

@@ -256,6 +256,9 @@ static int ensure_guides(rtg_handle* h) {
     const rtg_stats keep_stats = h->stats;
     const std::vector<double> keep_ms = h->launch_ms;
     const std::vector<unsigned long long> keep_rays = h->launch_rays;
+    // the guides stay one centre / pinhole sample each, whatever rtg_set_camera_sampling says
+    const rtg_camera_sampling keep_cam = h->cam_sampling;
+    (void)rtg_camera_sampling_defaults(&h->cam_sampling);
     h->count = h->timing = 0;
     int rc = RTG_OK;
     const int modes[2] = {RTG_INTEGRATOR_ALBEDO, RTG_INTEGRATOR_NORMALS};
@@ -272,6 +275,7 @@ static int ensure_guides(rtg_handle* h) {
     }
     h->d_film = keep_film;
     h->integrator = keep_int;
+    h->cam_sampling = keep_cam;
     h->count = keep_count;
     h->timing = keep_timing;
     h->stats = keep_stats;

@@ -297,6 +297,73 @@ RTG_D float pcg_next(uint64_t& s, uint64_t inc) {
     return (float)(pcg_step(s, inc) >> 8) * (1.0f / 16777216.0f);
 }
 
+// ------------------------------------------------------------------ camera sampling
+// rtg_set_camera_sampling (include/rtg.h): where sample `sample` of pixel `pixel` crosses the film
+// and the lens. The draws come from a PCG32 stream of their own, keyed like the path's but with the
+// seed xor 0x9E3779B97F4A7C15, so the path's stream (k_shade) draws what it draws without it. Four
+// draws in order, always all four: u0 (film x), u1 (film y), u2, u3 (lens). filter: 0 none, 1 box,
+// 2 tent (RTG_FILTER_*). IEEE float32 in the order written (no contraction); a zero offset leaves
+// k_generate's pixel-centre ray bit for bit.
+struct CamSampling {
+    int filter;
+    float filter_radius, lens_radius, focal_distance;
+};
+RTG_D float filter_offset(int filter, float r, float u) {
+    if (filter == 1) return (u * 2.0f - 1.0f) * r;
+    if (filter == 2) {
+        const float t = u < 0.5f ? sqrtf(2.0f * u) - 1.0f : 1.0f - sqrtf(2.0f - 2.0f * u);
+        return t * r;
+    }
+    return 0.0f;
+}
+// Camera::generateRay (Scene.h:43-54) at film position (px, py): the normalised direction
+RTG_D v3 camera_dir(const DevCamera& cam, float px, float py) {
+    float xp = px / cam.width;
+    float yp = 1.0f - (py / cam.height);
+    xp = (xp * 2.0f) - 1.0f;
+    yp = (yp * 2.0f) - 1.0f;
+    const float* m = cam.ip;
+    v3 dir = mk(((xp * m[0] + yp * m[1]) + 1.0f * m[2]) + m[3],
+                ((xp * m[4] + yp * m[5]) + 1.0f * m[6]) + m[7],
+                ((xp * m[8] + yp * m[9]) + 1.0f * m[10]) + m[11]);
+    const float* c = cam.cm;
+    dir = mk((dir.x * c[0] + dir.y * c[1]) + dir.z * c[2],
+             (dir.x * c[4] + dir.y * c[5]) + dir.z * c[6],
+             (dir.x * c[8] + dir.y * c[9]) + dir.z * c[10]);
+    return normalize(dir);
+}
+// (camera, pixel, sample, seed, setting) -> film position, ray origin and direction. Thin lens
+// (lens_radius R > 0, focal distance f), with xc, yc, zc the first three columns of camera.m:
+//   ft = f / fabsf(dot(d, zc))            P  = add(o, muls(d, ft))           (the point in focus)
+//   rr = R * sqrtf(u2)                    (s, c) = rtm_sincosf(6.2831855f * u3)
+//   o' = add(add(o, muls(xc, rr * c)), muls(yc, rr * s))                     d' = normalize(sub(P, o'))
+RTG_D void camera_sample(const DevCamera& cam, unsigned pixel, unsigned sample, uint64_t seed, const CamSampling& cs,
+                         float& fx, float& fy, v3& o, v3& d) {
+    const unsigned W = (unsigned)cam.width;
+    const unsigned x = pixel % W, y = pixel / W;
+    const uint64_t inc = pcg_inc(pixel, sample);
+    uint64_t st = pcg_seed(seed ^ 0x9E3779B97F4A7C15ull, inc);
+    const float u0 = pcg_next(st, inc);
+    const float u1 = pcg_next(st, inc);
+    const float u2 = pcg_next(st, inc);
+    const float u3 = pcg_next(st, inc);
+    fx = ((float)x + 0.5f) + filter_offset(cs.filter, cs.filter_radius, u0);
+    fy = ((float)y + 0.5f) + filter_offset(cs.filter, cs.filter_radius, u1);
+    o = mk(cam.ox, cam.oy, cam.oz);
+    d = camera_dir(cam, fx, fy);
+    if (cs.lens_radius > 0.0f) {
+        const float* c = cam.cm;
+        const v3 xc = mk(c[0], c[4], c[8]), yc = mk(c[1], c[5], c[9]), zc = mk(c[2], c[6], c[10]);
+        const float ft = cs.focal_distance / fabsf(dot(d, zc));
+        const v3 P = add(o, muls(d, ft));
+        const float rr = cs.lens_radius * sqrtf(u2);
+        float sn, cn;
+        rtm_sincosf(6.2831855f * u3, &sn, &cn);
+        o = add(add(o, muls(xc, rr * cn)), muls(yc, rr * sn));
+        d = normalize(sub(P, o));
+    }
+}
+
 // Sampler adaptors: the path's PCG stream, or a scripted list (probe / unit tests).
 struct PcgSampler {
     uint64_t s;

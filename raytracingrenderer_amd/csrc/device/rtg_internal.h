@@ -92,6 +92,8 @@ using namespace rtgd;
 #ifndef RTG_DEBUG
 #define RTG_DEBUG 0
 #endif
+#define RTG_CAM_PER_SAMPLE 1  // ChunkArgs::cam_mode bits (rtg_set_camera_sampling)
+#define RTG_CAM_LENS 2
 
 // Work counters of one bounce. Every field sits in its own 128-B line: the device-scope atomics on
 // them (queue appends in k_shade, work fetches in k_trace) are served one line at a time, so
@@ -169,6 +171,9 @@ struct ChunkArgs {
     int lean = 0;              // 1: bounce-0 state implied (identity queue, camera origin, thr 1,
                                // PCG seed, canHitLight); k_generate writes ray_d only
     unsigned seg_tiles = 0;    // tiles of 256 per queue segment (Counters::ne8); k_shade grid = 8x
+    int cam_mode = 0;          // rtg_set_camera_sampling: 0 one camera ray per pixel, shared by its samples
+                               // (k_generate, lean); RTG_CAM_PER_SAMPLE: one per path (k_generate_sampled:
+                               // ray_d[pid], hits[pid]); | RTG_CAM_LENS: and its origin in ray_o[pid]
     // path ids are pixel-major: pid = lp * ns + sl (a wave of camera rays is one pixel's samples)
     unsigned long long ns_mul = 0;  // lp = (pid * ns_mul) >> ns_shift (set_ns_div); 0: divide
     unsigned ns_shift = 0;
@@ -320,6 +325,7 @@ struct rtg_handle {
     float4* d_img = nullptr;   // the small-scene image (SceneView::img)
     int usew = 0, wide = 1;
     int integrator = RTG_INTEGRATOR_PATH;
+    rtg_camera_sampling cam_sampling{RTG_FILTER_NONE, 0.5f, 0.0f, 1.0f};  // rtg_set_camera_sampling
     bool rebuilt = false;     // wide tree cut from rebuild_over_leaves (else from the reference BVH2)
     uint32_t wide_depth = 0;  // wide levels on the longest root-to-leaf path
     DevTri48* d_tris48 = nullptr;
@@ -422,6 +428,18 @@ int flush_pending(rtg_handle* h);
 // the handle's stream waits for every queued chunk (called by every entry point that reads the film,
 // the stats or slot 0's buffers, or synchronises)
 int join_frames(rtg_handle* h);
+// the setting as the kernels take it, and its ChunkArgs::cam_mode
+static inline CamSampling cam_sampling_dev(const rtg_handle* h) {
+    const rtg_camera_sampling& c = h->cam_sampling;
+    return CamSampling{c.filter, c.filter_radius, c.lens_radius, c.focal_distance};
+}
+static inline int cam_mode_of(const rtg_handle* h) {
+    const rtg_camera_sampling& c = h->cam_sampling;
+    if (c.filter == RTG_FILTER_NONE && !(c.lens_radius > 0.0f)) return 0;
+    return RTG_CAM_PER_SAMPLE | (c.lens_radius > 0.0f ? RTG_CAM_LENS : 0);
+}
+// rtg_render.hip: RTG_ERR_ARG (with "who: ..." as the message) for a setting outside include/rtg.h's ranges
+int camera_sampling_check(const char* who, const rtg_camera_sampling* p);
 // k_generate for the paths of a (camera rays at pixel centres, Scene.h:43-54)
 int launch_generate(rtg_handle* h, const ChunkArgs& a, const PathBufs& pb, hipStream_t st);
 // rtg_denoise.hip: filter d_sum / spp (a film on h's device) with h's guides into h's result buffer,

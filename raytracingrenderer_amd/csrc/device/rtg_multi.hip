@@ -457,6 +457,17 @@ int rtg_group_set_options(rtg_group* g, int max_depth, int flags, uint32_t max_p
     return RTG_OK;
 }
 
+int rtg_group_set_camera_sampling(rtg_group* g, const rtg_camera_sampling* p) {
+    if (!g) { g_err = "rtg_group_set_camera_sampling: null group"; return RTG_ERR_ARG; }
+    // checked once for all ranks, so an argument error leaves every rank's setting as it was
+    if (int rc = camera_sampling_check("rtg_group_set_camera_sampling", p)) return rc;
+    for (rtg_handle* h : g->h) {
+        const int rc = rtg_set_camera_sampling(h, p);
+        if (rc) return rc;
+    }
+    return RTG_OK;
+}
+
 int rtg_group_render(rtg_group* g, uint32_t first_sample, uint32_t n_samples, uint64_t seed) {
     if (!g) return RTG_ERR_ARG;
     g->reduced = false;

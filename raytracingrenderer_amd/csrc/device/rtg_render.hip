@@ -79,6 +79,45 @@ __global__ __launch_bounds__(RTG_TB) void k_generate(ChunkArgs a, PathBufs p) {
     p.meta[pid] = 1 << 8;  // canHitLight = true
 }
 
+// rtg_set_camera_sampling with a filter or a lens: one thread per path, pixel-major (pid = lp * ns +
+// sl, a wave is still one pixel's samples). Each sample has a camera ray of its own (camera_sample,
+// rtg_dev.h) in ray_d[pid], and with a lens its origin in ray_o[pid] (the path id in .w, as later
+// bounces carry it); the rest of the bounce-0 state stays implied, as in k_generate's lean branch.
+// Bounce 0 is then a segmented queue of P rays at identity positions, like every later bounce.
+__global__ __launch_bounds__(RTG_TB) void k_generate_sampled(ChunkArgs a, PathBufs p, CamSampling cs) {
+    const unsigned pid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pid < 8) {  // the paths as queue segments (positions = path ids), as k_generate
+        const unsigned cap = a.seg_tiles * RTG_TB, lo = pid * cap;
+        p.ctr[0].ne8[32 * pid] = a.P > lo ? min(cap, a.P - lo) : 0u;
+    }
+    if (pid == 0) p.ctr[0].n_cam = a.P;  // camera rays traced: one per path (k_tally, rtg_launch_rays)
+    if (pid >= a.P) return;
+    unsigned lp, sl;
+    split_pid(a, pid, lp, sl);
+    float fx, fy;
+    v3 o, d;
+    camera_sample(a.cam, a.pixlist[lp], a.s0 + sl, a.seed, cs, fx, fy, o, d);
+    p.ray_d[pid] = make_float4(d.x, d.y, d.z, 0.0f);
+    if (a.cam_mode & RTG_CAM_LENS) p.ray_o[pid] = make_float4(o.x, o.y, o.z, __int_as_float((int)pid));
+}
+
+// rtg_probe_camera_samples: camera_sample on given (pixel, sample) pairs
+__global__ void k_probe_camera(DevCamera cam, CamSampling cs, unsigned long long seed, const unsigned* pixels,
+                               const unsigned* samples, unsigned n, float* rays, float* film_xy) {
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float fx, fy;
+    v3 o, d;
+    camera_sample(cam, pixels[i], samples[i], seed, cs, fx, fy, o, d);
+    float* r = rays + (size_t)i * 8;
+    r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = 0.0f;
+    r[4] = d.x; r[5] = d.y; r[6] = d.z; r[7] = 0.0f;
+    if (film_xy) {
+        film_xy[2 * (size_t)i] = fx;
+        film_xy[2 * (size_t)i + 1] = fy;
+    }
+}
+
 // ------------------------------------------------------------------ shade: rtg_shade.hip (k_shade, launch_shade)
 
 // ------------------------------------------------------------------ accumulate
@@ -482,6 +521,7 @@ static ChunkArgs chunk_args(const rtg_handle* h, uint32_t s0, uint32_t ns, uint6
     a.mode = h->integrator;
     a.cam = h->cam;
     a.lean = 1;
+    a.cam_mode = cam_mode_of(h);
     a.seg_tiles = (unsigned)seg_tiles(a.P);
     set_ns_div(a);
     return a;
@@ -510,15 +550,20 @@ static int shade_tiles(rtg_handle* h, const ChunkArgs& a, int b, bool hostgrid, 
 static void wire_bounce(TraceIO& io, const ChunkArgs& a, const PathBufs& pb, int b, int maxb) {
     // extension payload by queue position (set b & 1; null queue: path id = position);
     // bounce 0: the camera origin, directions from k_generate in set 0
+    // per-sample camera rays (rtg_set_camera_sampling): bounce 0 is wired like every later bounce,
+    // the P rays k_generate_sampled wrote as the eight segments ctr[0].ne8 at identity positions (a
+    // single counter would serialise 64M rays' fetches), their origins in ray_o with a lens
+    const bool cam_seg = b == 0 && a.cam_mode != 0;
+    const bool cam_one = b == 0 && a.cam_mode == 0;
     io.queue = nullptr;
-    io.ray_o = b == 0 ? nullptr : ((b & 1) ? pb.ray_o2 : pb.ray_o);
+    io.ray_o = b == 0 ? ((a.cam_mode & RTG_CAM_LENS) ? pb.ray_o : nullptr) : ((b & 1) ? pb.ray_o2 : pb.ray_o);
     io.cam_o = make_float4(a.cam.ox, a.cam.oy, a.cam.oz, 0.0f);
     io.ray_d = (b & 1) ? pb.ray_d2 : pb.ray_d;
-    // segmented queues; bounce 0: one queue of npix camera rays (a ray per pixel, shared by
-    // the pixel's samples) at identity positions, one work counter
-    io.count = b == 0 ? &pb.ctr[0].n_cam : nullptr;
-    io.seg_cap = b == 0 ? 0u : a.seg_tiles * RTG_TB;
-    io.seg_ne = (b > 0 && b < maxb) ? pb.ctr[b].ne8 : nullptr;
+    // segmented queues; bounce 0 by default: one queue of npix camera rays (a ray per pixel, shared
+    // by the pixel's samples) at identity positions, one work counter
+    io.count = cam_one ? &pb.ctr[0].n_cam : nullptr;
+    io.seg_cap = cam_one ? 0u : a.seg_tiles * RTG_TB;
+    io.seg_ne = ((b > 0 && b < maxb) || cam_seg) ? pb.ctr[b].ne8 : nullptr;
     io.seg_ns = b > 0 ? pb.ctr[b - 1].ns8 : nullptr;
     io.hits = pb.hits;
     io.squeue = pb.shq;
@@ -530,7 +575,7 @@ static void wire_bounce(TraceIO& io, const ChunkArgs& a, const PathBufs& pb, int
     io.contrib = b > 0 ? pb.contrib + (size_t)(b - 1) * a.P : nullptr;
     io.visible = nullptr;
     io.fetch = &pb.ctr[b].f_ext;
-    io.fetch8 = b == 0 ? nullptr : pb.ctr[b].f8;
+    io.fetch8 = cam_one ? nullptr : pb.ctr[b].f8;
 }
 
 // the wave slots of the largest k_trace grid (RTG_OPT_WAVETIME: three clocks per wave and launch)
@@ -552,8 +597,14 @@ static int issue_chunk(rtg_handle* h, ChunkSlot& sl, const ChunkArgs& a, int max
     timed_begin(h, ss, kinds.size());
     {
         RoctxRange r_gen("rtg:generate");
-        hipLaunchKernelGGL(k_generate, dim3((a.npix + RTG_TB - 1) / RTG_TB), dim3(RTG_TB), 0, ss, a, pb);  // lean: per pixel
-        LAUNCH_OK("k_generate");
+        if (a.cam_mode) {  // rtg_set_camera_sampling: a camera ray per path
+            hipLaunchKernelGGL(k_generate_sampled, dim3((a.P + RTG_TB - 1) / RTG_TB), dim3(RTG_TB), 0, ss, a, pb,
+                               cam_sampling_dev(h));
+            LAUNCH_OK("k_generate_sampled");
+        } else {
+            hipLaunchKernelGGL(k_generate, dim3((a.npix + RTG_TB - 1) / RTG_TB), dim3(RTG_TB), 0, ss, a, pb);  // lean: per pixel
+            LAUNCH_OK("k_generate");
+        }
     }
     timed_end(h, ss, kinds, 2);
     // Trace launch L_b (b = 0..maxb) carries the extension rays of bounce b (from shade(b-1),
@@ -588,7 +639,8 @@ static int issue_chunk(rtg_handle* h, ChunkSlot& sl, const ChunkArgs& a, int max
             // the camera launch (a ray per pixel, one work counter): no more one-wave blocks than it
             // has tail batches of rays, so waves without work do not queue their probes on the
             // counter (+0.5 %)
-            const unsigned cam_blocks = b == 0 ? std::max(8u, (a.npix + RTG_TAIL_BATCH - 1) / RTG_TAIL_BATCH) : 0u;
+            const unsigned cam_blocks =
+                (b == 0 && !a.cam_mode) ? std::max(8u, (a.npix + RTG_TAIL_BATCH - 1) / RTG_TAIL_BATCH) : 0u;
             if ((rc = launch_trace(h, io, ss, cam_blocks))) return rc;
         }
         timed_end(h, ss, kinds, 0);
@@ -738,7 +790,83 @@ int render_impl(rtg_handle* h, uint32_t first, uint32_t n_samples, uint64_t seed
     return h->timing ? collect_timing(h, maxb, kinds) : RTG_OK;
 }
 
+// RTG_ERR_ARG (with "who: ..." as the message) for a setting outside include/rtg.h's ranges
+int camera_sampling_check(const char* who, const rtg_camera_sampling* p) {
+    auto bad = [&](const char* what) {
+        g_err = std::string(who) + ": " + what;
+        return RTG_ERR_ARG;
+    };
+    if (!p) return bad("null argument");
+    if (p->filter < RTG_FILTER_NONE || p->filter > RTG_FILTER_TENT) return bad("unknown filter");
+    if (!std::isfinite(p->filter_radius) || p->filter_radius < 0.0f || p->filter_radius > RTG_FILTER_MAX_RADIUS)
+        return bad("filter_radius must be finite and in [0, RTG_FILTER_MAX_RADIUS]");
+    if (!std::isfinite(p->lens_radius) || p->lens_radius < 0.0f) return bad("lens_radius must be finite and >= 0");
+    if (p->lens_radius > 0.0f && !(std::isfinite(p->focal_distance) && p->focal_distance > 0.0f))
+        return bad("focal_distance must be finite and > 0 with a lens");
+    return RTG_OK;
+}
+
 extern "C" {
+
+int rtg_camera_sampling_defaults(rtg_camera_sampling* p) {
+    if (!p) { g_err = "rtg_camera_sampling_defaults: null argument"; return RTG_ERR_ARG; }
+    *p = rtg_camera_sampling{RTG_FILTER_NONE, 0.5f, 0.0f, 1.0f};
+    return RTG_OK;
+}
+
+int rtg_set_camera_sampling(rtg_handle* h, const rtg_camera_sampling* p) {
+    if (!h) { g_err = "rtg_set_camera_sampling: null handle"; return RTG_ERR_ARG; }
+    if (int rc = camera_sampling_check("rtg_set_camera_sampling", p)) return rc;
+    HIPOK(hipSetDevice(h->device));
+    if (int rc = join_frames(h)) return rc;  // queued calls render with the settings they were queued under
+    HIPOK(hipStreamSynchronize(h->stream));
+    h->cam_sampling = *p;
+    return RTG_OK;
+}
+
+int rtg_get_camera_sampling(rtg_handle* h, rtg_camera_sampling* p) {
+    if (!h || !p) { g_err = "rtg_get_camera_sampling: null argument"; return RTG_ERR_ARG; }
+    *p = h->cam_sampling;
+    return RTG_OK;
+}
+
+int rtg_probe_camera_samples(rtg_handle* h, const uint32_t* pixels, const uint32_t* samples, uint32_t n,
+                             uint64_t seed, float* rays, float* film_xy) {
+    if (!h || !pixels || !samples || !rays) { g_err = "rtg_probe_camera_samples: null argument"; return RTG_ERR_ARG; }
+    if (n > 0x7fffffffu / 8u) { g_err = "rtg_probe_camera_samples: too many cases"; return RTG_ERR_ARG; }
+    const uint64_t npix = (uint64_t)h->W * (uint64_t)h->H;
+    for (uint32_t i = 0; i < n; ++i)
+        if (pixels[i] >= npix || samples[i] >= RTG_MAX_SAMPLES_PER_KEY) {
+            g_err = "rtg_probe_camera_samples: pixel or sample index out of range";
+            return RTG_ERR_ARG;
+        }
+    if (n == 0) return RTG_OK;
+    HIPOK(hipSetDevice(h->device));
+    unsigned *d_pix = nullptr, *d_smp = nullptr;
+    float *d_rays = nullptr, *d_xy = nullptr;
+    auto run = [&]() -> int {
+        HIPOK(hipMalloc((void**)&d_pix, (size_t)n * sizeof(unsigned)));
+        HIPOK(hipMalloc((void**)&d_smp, (size_t)n * sizeof(unsigned)));
+        HIPOK(hipMalloc((void**)&d_rays, (size_t)n * 8 * sizeof(float)));
+        HIPOK(hipMalloc((void**)&d_xy, (size_t)n * 2 * sizeof(float)));
+        HIPOK(hipMemcpy(d_pix, pixels, (size_t)n * sizeof(unsigned), hipMemcpyHostToDevice));
+        HIPOK(hipMemcpy(d_smp, samples, (size_t)n * sizeof(unsigned), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_probe_camera, dim3((n + 255) / 256), dim3(256), 0, nullptr, h->cam, cam_sampling_dev(h),
+                           (unsigned long long)seed, (const unsigned*)d_pix, (const unsigned*)d_smp, (unsigned)n, d_rays,
+                           d_xy);
+        HIPOK(hipGetLastError());
+        HIPOK(hipDeviceSynchronize());
+        HIPOK(hipMemcpy(rays, d_rays, (size_t)n * 8 * sizeof(float), hipMemcpyDeviceToHost));
+        if (film_xy) HIPOK(hipMemcpy(film_xy, d_xy, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost));
+        return RTG_OK;
+    };
+    const int rc = run();
+    (void)hipFree(d_pix);
+    (void)hipFree(d_smp);
+    (void)hipFree(d_rays);
+    (void)hipFree(d_xy);
+    return rc;
+}
 
 int rtg_render_async(rtg_handle* h, uint32_t first, uint32_t n, uint64_t seed, const uint32_t* tiles,
                      uint32_t n_tiles, void* stream) {

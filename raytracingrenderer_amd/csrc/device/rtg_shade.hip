@@ -78,11 +78,11 @@ __global__ __launch_bounds__(RTG_TB, RTG_SHADE_WAVES) void k_shade(SceneView s, 
         DevShade S;
         if (valid) {
             unsigned j = i;  // bounce 0: the pixel's camera ray and first hit (k_generate), shared by its samples
-            if (lean0) {
+            if (lean0 && !a.cam_mode) {  // (per-sample camera rays, k_generate_sampled: the path's own)
                 unsigned sl0;
                 split_pid(a, i, j, sl0);
             }
-            if (!lean0) ro = in_o[i];
+            if (!lean0 || (a.cam_mode & RTG_CAM_LENS)) ro = in_o[i];  // (a lens: the sample's origin)
             rd = in_d[j];
             h = p.hits[j];
             if (h.x < RTG_FLT_MAX) S = s.shade[__float_as_int(h.y)];

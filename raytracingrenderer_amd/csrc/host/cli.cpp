@@ -20,6 +20,10 @@
 // (-outputFilename's name when given, else result_<spp>); optional -denoiseIterations (5),
 // -denoiseSigmaColour (1), -denoiseSigmaAlbedo (0.1). The normal output is unchanged. With -gpus /
 // -devices it goes through rtg_group_denoise.
+// Anti-aliasing and depth of field (rtg_set_camera_sampling, include/rtg.h): -pixelFilter none|box|tent
+// (none: every sample through the pixel centre, the reference's renderTile), -filterRadius r (pixels;
+// default 0.5 for box, 1 for tent), -lensRadius R (0: pinhole) and -focalDistance f, for one device
+// and for -gpus / -devices alike.
 // Multi-GPU (one node): -gpus N renders on devices 0..N-1, -devices a,b,... on a list. Rank r
 // renders the 32x32 tiles with (tile_x + tile_y) % N == r, and the film is assembled on the first
 // device from every device's own tiles (packed, one RCCL send per device, scattered) before it is
@@ -84,15 +88,28 @@ int main(int argc, char** argv) {
     } else if (args.count("-gpus")) {
         for (int i = 0; i < std::stoi(args["-gpus"]); ++i) devices.push_back(i);
     }
+    // -pixelFilter none|box|tent -filterRadius r -lensRadius R -focalDistance f (rtg_set_camera_sampling)
+    rtg_camera_sampling cs{};
+    rtg_camera_sampling_defaults(&cs);
+    const std::string pf = get("-pixelFilter", "none");
+    if (pf == "none") cs.filter = RTG_FILTER_NONE;
+    else if (pf == "box") cs.filter = RTG_FILTER_BOX;
+    else if (pf == "tent") cs.filter = RTG_FILTER_TENT;
+    else return die("-pixelFilter", "one of none, box, tent");
+    cs.filter_radius = std::stof(get("-filterRadius", cs.filter == RTG_FILTER_TENT ? "1" : "0.5"));
+    cs.lens_radius = std::stof(get("-lensRadius", "0"));
+    cs.focal_distance = std::stof(get("-focalDistance", "1"));
     rtg_handle* rt = nullptr;
     rtg_group* grp = nullptr;
     if (devices.empty()) {
         if (rtg_create(device, rth_scene_desc(scene), &rt) != 0) return die("rtg_create", rtg_last_error());
         if (rtg_set_options(rt, max_depth, RTG_OPT_CULL, 0) != 0) return die("rtg_set_options", rtg_last_error());
+        if (rtg_set_camera_sampling(rt, &cs) != 0) return die("rtg_set_camera_sampling", rtg_last_error());
     } else {
         if (rtg_group_create(devices.data(), (int)devices.size(), rth_scene_desc(scene), &grp) != 0)
             return die("rtg_group_create", rtg_last_error());
         if (rtg_group_set_options(grp, max_depth, RTG_OPT_CULL, 0) != 0) return die("rtg_group_set_options", rtg_last_error());
+        if (rtg_group_set_camera_sampling(grp, &cs) != 0) return die("rtg_group_set_camera_sampling", rtg_last_error());
         std::printf("%d devices, own-tile film exchange by %s\n", (int)devices.size(),
                     rtg_group_uses_rccl(grp) ? "RCCL (ncclSend/ncclRecv)"
                     : devices.size() == 1    ? "none (one device)"

@@ -136,8 +136,14 @@ def reduce_film(film_tensor, dist, dst=0):
     return film_tensor
 
 
-def render_sharded(rt, n_samples, rank, world, dist=None, film_tensor=None, first_sample=0, exchange=None):
+def render_sharded(rt, n_samples, rank, world, dist=None, film_tensor=None, first_sample=0, exchange=None,
+                   camera_sampling=None):
     """Render this rank's tiles with RayTracer `rt`, then assemble the film on rank 0.
+
+    camera_sampling: a dict of RayTracer.set_camera_sampling's arguments (e.g. {"filter": "tent"}),
+    applied to this rank's tracer before it renders; every rank must pass the same one (the camera
+    stream is keyed by pixel and sample, so the ranks' tiles then fit together as on one device).
+    None leaves the tracer's setting as it is.
 
     world > 1: rank 0's film_tensor (torch float32 HxWx3) receives the whole film from every rank's
     own tiles (FilmExchange; pass `exchange` to reuse its buffers across calls); a CUDA tensor is
@@ -146,6 +152,8 @@ def render_sharded(rt, n_samples, rank, world, dist=None, film_tensor=None, firs
     whole-film reduce of rounds 1-4 left it. Returns film_tensor.
     world == 1: returns film_tensor filled with the film if given, else the film as a numpy array."""
     tiles = tiles_for_rank(rt.width, rt.height, rank, world)
+    if camera_sampling is not None:
+        rt.set_camera_sampling(**camera_sampling)
     rt.render(n_samples, tiles=tiles, first_sample=first_sample)
     if film_tensor is None:
         if world > 1:

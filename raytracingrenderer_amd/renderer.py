@@ -195,6 +195,23 @@ def probe_texture(texels, coords, env=False, uniform=False):
     return out
 
 
+FILTERS = {"none": N.RTG_FILTER_NONE, "box": N.RTG_FILTER_BOX, "tent": N.RTG_FILTER_TENT}
+FILTER_DEFAULT_RADIUS = {N.RTG_FILTER_NONE: 0.5, N.RTG_FILTER_BOX: 0.5, N.RTG_FILTER_TENT: 1.0}
+
+
+def _camera_sampling(filter, filter_radius, lens_radius, focal_distance):
+    """The rtg_camera_sampling of set_camera_sampling's arguments (filter: a name of FILTERS or an
+    RTG_FILTER_* value; filter_radius None: the filter's default). Range errors are the library's."""
+    if isinstance(filter, str):
+        if filter not in FILTERS:
+            raise ValueError("unknown pixel filter %r (one of %s)" % (filter, ", ".join(FILTERS)))
+        filter = FILTERS[filter]
+    filter = int(filter)
+    if filter_radius is None:
+        filter_radius = FILTER_DEFAULT_RADIUS.get(filter, 0.5)
+    return N.rtg_camera_sampling(filter, float(filter_radius), float(lens_radius), float(focal_distance))
+
+
 class RayTracer:
     """RayTracer (Renderer.h:31-899) backed by librtg on one GPU."""
 
@@ -225,6 +242,39 @@ class RayTracer:
         mode = self.INTEGRATORS[integrator] if isinstance(integrator, str) else int(integrator)
         _check(self._lib.rtg_set_integrator(self._h, mode), self._lib.rtg_last_error)
         self.integrator = integrator
+
+    def set_camera_sampling(self, filter="none", filter_radius=None, lens_radius=0.0, focal_distance=1.0):
+        """Anti-aliasing and depth of field (rtg_set_camera_sampling). filter "none" (default: every
+        sample through the pixel centre, as renderTile), "box" or "tent": sample s of a pixel crosses
+        the film at an offset drawn from the filter (radius in pixels; None: 0.5 for the box, 1 for
+        the tent) and still counts for its own pixel only. lens_radius > 0: a thin lens focused at
+        focal_distance along the view direction. Applies to render(), adaptiveRender() and every
+        integrator; not to lightTracer(), instantRadiosity() or the denoiser's guides."""
+        p = _camera_sampling(filter, filter_radius, lens_radius, focal_distance)
+        _check(self._lib.rtg_set_camera_sampling(self._h, C.byref(p)), self._lib.rtg_last_error)
+
+    def camera_sampling(self):
+        """The current setting: {"filter": name, "filter_radius", "lens_radius", "focal_distance"}."""
+        p = N.rtg_camera_sampling()
+        _check(self._lib.rtg_get_camera_sampling(self._h, C.byref(p)), self._lib.rtg_last_error)
+        names = {v: k for k, v in FILTERS.items()}
+        return {"filter": names.get(p.filter, p.filter), "filter_radius": p.filter_radius,
+                "lens_radius": p.lens_radius, "focal_distance": p.focal_distance}
+
+    def camera_samples(self, pixels, samples, seed=None):
+        """The camera rays the renderer generates for the given (pixel index y * W + x, sample index)
+        pairs under the current setting (rtg_probe_camera_samples; seed None: this tracer's).
+        Returns (rays (n, 8) = o.xyz, 0, d.xyz, 0 as trace_closest takes them, film_xy (n, 2))."""
+        px = np.ascontiguousarray(pixels, np.uint32).reshape(-1)
+        sm = np.ascontiguousarray(samples, np.uint32).reshape(-1)
+        if len(px) != len(sm):
+            raise ValueError("camera_samples: pixels and samples must have one length")
+        rays = np.zeros((len(px), 8), np.float32)
+        xy = np.zeros((len(px), 2), np.float32)
+        _check(self._lib.rtg_probe_camera_samples(self._h, N.ptr(px, C.c_uint32), N.ptr(sm, C.c_uint32), len(px),
+                                                  self.seed if seed is None else seed, N.ptr(rays, C.c_float),
+                                                  N.ptr(xy, C.c_float)), self._lib.rtg_last_error)
+        return rays, xy
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -419,6 +469,11 @@ class RayTracerGroup:
             self.flags = flags
         _check(self._lib.rtg_group_set_options(self._g, self.max_depth, self.flags, max_paths),
                self._lib.rtg_last_error)
+
+    def set_camera_sampling(self, filter="none", filter_radius=None, lens_radius=0.0, focal_distance=1.0):
+        """RayTracer.set_camera_sampling on every rank (rtg_group_set_camera_sampling)."""
+        p = _camera_sampling(filter, filter_radius, lens_radius, focal_distance)
+        _check(self._lib.rtg_group_set_camera_sampling(self._g, C.byref(p)), self._lib.rtg_last_error)
 
     def setup_ms(self):
         """(host build of the device records, parallel uploads) of rtg_group_create, in ms."""

@@ -39,7 +39,8 @@ extern "C" {
  * 6: rtg_group_render_async / rtg_group_reduce_async / rtg_group_synchronize (queued group frames);
  *    rtg_film_scatter takes the film's pixel count; rtg_stats.lane_idle_* appended
  *    (additive, still 6: the denoiser, rtg_denoise_* and rtg_group_denoise; camera sampling,
- *    rtg_*_camera_sampling and rtg_probe_camera_samples) */
+ *    rtg_*_camera_sampling and rtg_probe_camera_samples; environment light sampling,
+ *    rtg_*_env_sampling, rtg_env_* and rtg_probe_env_samples) */
 #define RTG_ABI_VERSION 6
 
 /* error codes */
@@ -236,6 +237,76 @@ int  rtg_get_camera_sampling(rtg_handle* h, rtg_camera_sampling* p);
 int  rtg_probe_camera_samples(rtg_handle* h, const uint32_t* pixels, const uint32_t* samples, uint32_t n,
                               uint64_t seed, float* rays, float* film_xy);
 
+/* ---- environment light sampling (rtg_env.hip). EnvironmentMap::sample draws every NEE
+ * direction towards the environment uniformly over the sphere (Lights.h:143-149; the reference leaves
+ * luminance weighting as an assignment, :160). That is the default here, RTG_ENV_UNIFORM, untouched:
+ * the same kernels, draws and bits. RTG_ENV_LUMINANCE draws (wi, pdf) from a piecewise-constant density
+ * proportional to the map's filtered luminance times sin theta, through an alias table (one 16-byte
+ * load per sample). Definition, for a W x H environment texture (N = W * H cells):
+ *   cell (cx, cy)  the (u, v) with u W in [cx, cx+1), v H in [cy, cy+1): the footprint in which
+ *                  Texture::sample (Imaging.h:72-94) blends texels (cx, cy), (cx+1 mod W, cy),
+ *                  (cx, cy+1 mod H), (cx+1 mod W, cy+1 mod H)
+ *   weight         w = (double)m * sin(pi * (cy + 0.5) / H) in binary64 (pi = M_PI, the product first),
+ *                  m = the maximum over those four texels of Colour::Lum =
+ *                  ((0.2126f r) + (0.7152f g)) + (0.0722f b) in float32, a negative or non-finite Lum
+ *                  counting as 0. The maximum makes the density positive wherever the bilinear lookup
+ *                  can return light (the estimator stays unbiased); a per-texel luminance would leave
+ *                  the cell beside a bright texel at zero density.
+ *   sum            the weights added in index order (k = cy * W + cx) in binary64
+ *   table          N entries {prob (float), alias (uint32), cellpdf_self (float), cellpdf_alias (float)},
+ *                  cellpdf_k = (float)(((w_k / sum) * N) / ((2.0 * pi) * pi)), built by Vose's algorithm
+ *                  in binary64 (p_k = (w_k / sum) * N; prob is its keep probability rounded to float);
+ *                  for every cell i, prob_i / N + sum over {j: alias_j = i} of (1 - prob_j) / N is
+ *                  w_i / sum (to binary64 rounding before prob is rounded to float, which moves it by
+ *                  at most 2^-25 / N per entry involved); a zero-weight cell has prob == 0 exactly.
+ *   draws          the environment branch of the light sample takes four draws from the path's own PCG
+ *                  stream, in this order and always all four: r0, the raw 32-bit output of a PCG step,
+ *                  then d1, d2, d3, floats in [0, 1) as every other draw. (The uniform branch keeps its
+ *                  two, so the two modes' path streams differ after the first environment sample.)
+ *   sample         k = (uint32)(((uint64)r0 * N) >> 32); e = table[k]; keep = d1 < e.prob;
+ *                  c = keep ? k : e.alias; cp = keep ? e.cellpdf_self : e.cellpdf_alias;
+ *                  cx = c % W, cy = c / W; u = ((float)cx + d2) / (float)W; v = ((float)cy + d3) / (float)H;
+ *                  theta = 3.14159265f * v; phi = 6.2831855f * u; (st, ct) = sincosf(theta),
+ *                  (sp, cp') = sincosf(phi) of include/rtg_math.h; wi = (st * cp', ct, st * sp), the
+ *                  inverse of EnvironmentMap::evaluate's (atan2f(z, x), acosf(y)); pdf = cp / st.
+ *                  !(st > 0) or !(pdf > 0): the sample contributes nothing (no shadow ray).
+ *                  IEEE float32 in the order written, no contraction. The radiance stays the one
+ *                  EnvironmentMap::evaluate(wi), and the shadow ray and Ld = f E g / (pmf pdf) stay as
+ *                  they are (pmf = 1 / n_lights: no power-weighted light selection, no MIS with
+ *                  BSDF-sampled environment hits).
+ *   unevenness     the integer cell pick gives each entry floor or ceil of 2^32 / N of the 2^32 values of
+ *                  r0: uneven by at most N / 2^32 relative (under 0.05 % for a 2048 x 1024 map).
+ * A scene without an environment light, or a map whose weights sum to 0, accepts the mode and keeps
+ * sampling uniformly, with the launches it has today. W * H > RTG_ENV_MAX_CELLS: RTG_ERR_ARG
+ * (rtg_env_sampling_check is the setter's argument check alone). The table is built on the first
+ * RTG_ENV_LUMINANCE setting of a handle (a small kernel takes the footprint maxima from the texels on
+ * the device, the host runs Vose and uploads the entries) and is kept until rtg_destroy; every rank
+ * of a group builds its own, the same bits. rtg_set_env_sampling first issues and waits for queued
+ * frames; an argument error leaves the previous setting in place.
+ * The setting applies to rtg_render, rtg_render_async, rtg_render_adaptive and the group calls, under
+ * RTG_INTEGRATOR_PATH, _DIRECT and _DIRECT_MIS (kernels of their own, k_shade_env; the default's are
+ * not touched). It does not apply to rtg_render_light and rtg_render_instant_radiosity (their
+ * sampleDirectionFromLight / samplePositionFromLight stay uniform) or to the denoiser's guides, which
+ * sample no light. */
+#define RTG_ENV_UNIFORM   0
+#define RTG_ENV_LUMINANCE 1
+#define RTG_ENV_MAX_CELLS 16777216u  /* 2^24 */
+int  rtg_env_sampling_check(int mode, uint32_t env_width, uint32_t env_height);
+int  rtg_set_env_sampling(rtg_handle* h, int mode);
+int  rtg_get_env_sampling(rtg_handle* h, int* mode);
+/* The active table: *w, *h its size (0, 0 when no table is active: uniform mode, no environment light,
+ * a black map), entries (or NULL) w*h*4 32-bit words, build_ms (or NULL) the host time of its build. */
+int  rtg_env_table(rtg_handle* h, uint32_t* w, uint32_t* height, float* entries, double* build_ms);
+/* The w*h cell weights the active table was built from (RTG_ERR_ARG when none is active). */
+int  rtg_env_weights(rtg_handle* h, double* weights);
+/* The kernel's own sampling function on n scripted draws (r0[n], d[n*3] = d1, d2, d3) against the
+ * active table: out n*4 = wi.xyz, pdf (0 where the sample is rejected). No active table: RTG_ERR_ARG. */
+int  rtg_probe_env_samples(rtg_handle* h, const uint32_t* r0, const float* d, uint32_t n, float* out);
+/* The host's table builder alone (no device call): Vose on n weights; prob (binary64) and alias per
+ * entry, and the n*4 words of the entries as uploaded. Weights summing to 0, n == 0 or
+ * n > RTG_ENV_MAX_CELLS: RTG_ERR_ARG. */
+int  rtg_env_alias_build(const double* weights, uint32_t n, double* prob, uint32_t* alias, float* entries);
+
 /* Add samples [first_sample, first_sample+n_samples) of every pixel in the listed 32x32 tiles
  * (tile id = ty*tilesX + tx, RTBase TILE_SIZE=32; tile_ids=NULL = all tiles) to the film, in
  * sample order per pixel. Equivalent to n_samples calls of RayTracer::render() with the
@@ -325,6 +396,7 @@ int  rtg_group_size(rtg_group* g);
 rtg_handle* rtg_group_handle(rtg_group* g, int rank);  /* e.g. for rtg_get_stats; owned by the group */
 int  rtg_group_set_options(rtg_group* g, int max_depth, int flags, uint32_t max_paths);
 int  rtg_group_set_camera_sampling(rtg_group* g, const rtg_camera_sampling* p);  /* every rank's handle */
+int  rtg_group_set_env_sampling(rtg_group* g, int mode);  /* rtg_set_env_sampling on every rank's handle */
 int  rtg_group_render(rtg_group* g, uint32_t first_sample, uint32_t n_samples, uint64_t seed);
 int  rtg_group_reduce(rtg_group* g);  /* the films stay per device; the assembled film goes to a separate buffer */
 /* Queued forms (the frame loop of Main.cpp:74-118 on N devices). rtg_group_render_async is every

@@ -17,6 +17,8 @@ RTG_INTEGRATOR_DIRECT_MIS = 4
 RTG_PROBE_TEX_SAMPLE, RTG_PROBE_TEX_ENV, RTG_PROBE_TEX_UNIFORM = 0, 1, 2
 RTG_FILTER_NONE, RTG_FILTER_BOX, RTG_FILTER_TENT = 0, 1, 2
 RTG_FILTER_MAX_RADIUS = 4.0
+RTG_ENV_UNIFORM, RTG_ENV_LUMINANCE = 0, 1
+RTG_ENV_MAX_CELLS = 1 << 24
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
@@ -154,6 +156,15 @@ RTG_EXPORTS = [
     ("rtg_get_camera_sampling", C.c_int, [C.c_void_p, C.POINTER(rtg_camera_sampling)]),
     ("rtg_group_set_camera_sampling", C.c_int, [C.c_void_p, C.POINTER(rtg_camera_sampling)]),
     ("rtg_probe_camera_samples", C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32, C.c_uint64, f32p, f32p]),
+    # environment light sampling: the luminance alias table (rtg_env.hip)
+    ("rtg_env_sampling_check", C.c_int, [C.c_int, C.c_uint32, C.c_uint32]),
+    ("rtg_set_env_sampling", C.c_int, [C.c_void_p, C.c_int]),
+    ("rtg_get_env_sampling", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    ("rtg_group_set_env_sampling", C.c_int, [C.c_void_p, C.c_int]),
+    ("rtg_env_table", C.c_int, [C.c_void_p, u32p, u32p, f32p, C.POINTER(C.c_double)]),
+    ("rtg_env_weights", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    ("rtg_probe_env_samples", C.c_int, [C.c_void_p, u32p, f32p, C.c_uint32, f32p]),
+    ("rtg_env_alias_build", C.c_int, [C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), u32p, f32p]),
 ]
 
 RTH_EXPORTS = [

@@ -123,6 +123,11 @@ int upload_scene(int device, const HostScene& hs, rtg_handle* h) {
     s.img_lb = hs.img_lb;
     for (int k = 0; k < 6; ++k) s.root_box[k] = hs.root_box[k];
     s.cull_scale = hs.cull_scale;
+    for (const DevLight& L : hs.lights) {  // v1t.w: the light's type bits, 1 = the environment light
+        int type;
+        std::memcpy(&type, &L.v1t.w, 4);
+        h->env_light = h->env_light || type == 1;
+    }
     h->cam = hs.cam;
     h->proj = hs.proj;
     h->W = (int)hs.cam.width;
@@ -189,6 +194,7 @@ void rtg_destroy(rtg_handle* h) {
     }
     if (h->entry) (void)hipEventDestroy(h->entry);
     denoise_release(h);
+    (void)hipFree(h->d_env_table);
     (void)hipFree(h->d_img);
     (void)hipFree(h->d_nodes); (void)hipFree(h->d_nodesq); (void)hipFree(h->d_leafbox); (void)hipFree(h->d_tris48); (void)hipFree(h->d_shade); (void)hipFree(h->d_mats);
     (void)hipFree(h->d_lights); (void)hipFree(h->d_texinfo); (void)hipFree(h->d_texels); (void)hipFree(h->d_film);

@@ -297,6 +297,40 @@ RTG_D float pcg_next(uint64_t& s, uint64_t inc) {
     return (float)(pcg_step(s, inc) >> 8) * (1.0f / 16777216.0f);
 }
 
+// ------------------------------------------------------------------ environment light sampling
+// rtg_set_env_sampling(.., RTG_ENV_LUMINANCE) (include/rtg.h has the definition): a direction from the
+// piecewise-constant density proportional to the environment map's filtered luminance times sin
+// theta, through an alias table over the map's w x h cells: one 16-B load. entry = {prob, alias,
+// cellpdf_self, cellpdf_alias}, cellpdf = the cell's probability * n / (2 pi^2), so the solid-angle
+// density at polar angle theta is cellpdf / sin theta. r0: a raw 32-bit draw; d1, d2, d3: floats
+// in [0, 1). IEEE float32 in the order written (no contraction). False (pdf 0): the sample
+// contributes nothing. k_shade_env's light sample and k_probe_env share this body.
+struct EnvTable {
+    const uint4* table;  // null: no table (uniform sampling)
+    unsigned n, w, h;    // n = w * h <= 2^24
+};
+RTG_D bool env_sample_luminance(const EnvTable& e, uint32_t r0, float d1, float d2, float d3, v3& wi, float& pdf) {
+    const uint32_t k = (uint32_t)(((uint64_t)r0 * e.n) >> 32);
+    const uint4 t = e.table[k];
+    const bool keep = d1 < __uint_as_float(t.x);
+    const uint32_t c = keep ? k : t.y;
+    const float cp = __uint_as_float(keep ? t.z : t.w);
+    const uint32_t cy = c / e.w, cx = c - cy * e.w;
+    const float u = ((float)cx + d2) / (float)e.w;
+    const float v = ((float)cy + d3) / (float)e.h;
+    const float theta = 3.14159265f * v, phi = 6.2831855f * u;
+    float st, ct, sp, cph;
+    rtm_sincosf(theta, &st, &ct);
+    rtm_sincosf(phi, &sp, &cph);
+    wi = mk(st * cph, ct, st * sp);  // the inverse of EnvironmentMap::evaluate's (atan2f(z, x), acosf(y))
+    pdf = cp / st;
+    if (!(st > 0.0f) || !(pdf > 0.0f)) {
+        pdf = 0.0f;
+        return false;
+    }
+    return true;
+}
+
 // ------------------------------------------------------------------ camera sampling
 // rtg_set_camera_sampling (include/rtg.h): where sample `sample` of pixel `pixel` crosses the film
 // and the lens. The draws come from a PCG32 stream of their own, keyed like the path's but with the

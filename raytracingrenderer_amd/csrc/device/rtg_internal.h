@@ -70,6 +70,9 @@ using namespace rtgd;
 #ifndef RTG_SHADE_WAVES
 #define RTG_SHADE_WAVES 7   // min waves per SIMD for k_shade (72 VGPRs, no spills; one tile per block)
 #endif
+#ifndef RTG_SHADE_ENV_ALT_WAVES
+#define RTG_SHADE_ENV_ALT_WAVES 4  // k_shade_env<true, *> (RTG_ENV_LUMINANCE under DIRECT / DIRECT_MIS): 108
+#endif                             // VGPRs, no spills (5: 2-10 spilled, 7: 48-77)
 // The own binary tree the wide nodes are cut from (prepare_scene; rtg_bvh.hip for spatial splits)
 #ifndef RTG_SAH_SWEEP
 #define RTG_SAH_SWEEP 2048  // full SAH sweep up to this many primitives in a node, binned above
@@ -368,6 +371,15 @@ struct rtg_handle {
     int cap_cnt = 0;
     std::vector<hipEvent_t> tev;  // [b]: k_trace(b) has finished (a launch that never wrote its counts)
     DenoiseState* dn = nullptr;   // denoiser buffers and cached guides, allocated by the first rtg_denoise*
+    // rtg_set_env_sampling (rtg_env.hip): the alias table over the environment map's cells, built by the
+    // first RTG_ENV_LUMINANCE setting and kept until rtg_destroy
+    int env_mode = RTG_ENV_UNIFORM;
+    bool env_light = false;       // the light list holds the environment light (upload_scene)
+    bool env_built = false;       // the build has run (a black map leaves no table: the sampler stays uniform)
+    uint4* d_env_table = nullptr;
+    std::vector<uint32_t> env_entries;  // the table's host copy (rtg_env_table)
+    std::vector<double> env_weights;    // the cell weights it was built from (rtg_env_weights)
+    double env_build_ms = 0.0;          // host time of the build: weights kernel, copy, Vose, upload
 };
 #define RTG_CNT_PENDING 0xFFFFFFFFu
 
@@ -449,6 +461,10 @@ int denoise_film(rtg_handle* h, const float* d_sum, uint32_t spp, const rtg_deno
 int denoise_check_params(const char* who, const rtg_denoise_params* p);
 // frees the handle's denoiser state (rtg_destroy)
 void denoise_release(rtg_handle* h);
+// rtg_env.hip: the table k_shade_env samples the environment light from under the handle's setting and
+// integrator, or one with a null pointer (uniform sampling: today's k_shade launches)
+EnvTable env_table_of(const rtg_handle* h);
 // rtg_shade.hip: one k_shade launch of `grid` blocks (ALT = alt, TAB = tab) for bounce b
+// (env with a table: k_shade_env, the ALT kernel with the environment light's alias-table sample)
 int launch_shade(bool alt, bool tab, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
-                 const PathBufs& p, int b);
+                 const PathBufs& p, int b, const EnvTable* env = nullptr);

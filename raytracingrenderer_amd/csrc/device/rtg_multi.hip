@@ -468,6 +468,26 @@ int rtg_group_set_camera_sampling(rtg_group* g, const rtg_camera_sampling* p) {
     return RTG_OK;
 }
 
+int rtg_group_set_env_sampling(rtg_group* g, int mode) {
+    if (!g) { g_err = "rtg_group_set_env_sampling: null group"; return RTG_ERR_ARG; }
+    // checked once for all ranks (they hold the same scene), so an argument error leaves every rank's
+    // setting as it was; every rank builds its own table, the same bits from the same texels
+    if (int rc = rtg_env_sampling_check(mode, 0, 0)) return rc;
+    for (rtg_handle* h : g->h) {
+        int prev = RTG_ENV_UNIFORM;
+        (void)rtg_get_env_sampling(h, &prev);
+        const int rc = rtg_set_env_sampling(h, mode);
+        if (rc) {
+            for (rtg_handle* u : g->h) {
+                if (u == h) break;
+                (void)rtg_set_env_sampling(u, prev);
+            }
+            return rc;
+        }
+    }
+    return RTG_OK;
+}
+
 int rtg_group_render(rtg_group* g, uint32_t first_sample, uint32_t n_samples, uint64_t seed) {
     if (!g) return RTG_ERR_ARG;
     g->reduced = false;

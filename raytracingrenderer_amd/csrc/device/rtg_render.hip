@@ -618,7 +618,8 @@ static int issue_chunk(rtg_handle* h, ChunkSlot& sl, const ChunkArgs& a, int max
                 timed_begin(h, ss, kinds.size());
                 const bool tab = h->sv.n_mats <= RTG_LDS_MATS && h->sv.n_lights <= RTG_LDS_LIGHTS;
                 const bool alt = h->integrator != RTG_INTEGRATOR_PATH;
-                if ((rc = launch_shade(alt, tab, 8 * tiles, ss, h->sv, a, pb, b - 1))) return rc;
+                const EnvTable et = env_table_of(h);  // RTG_ENV_LUMINANCE with a table: k_shade_env
+                if ((rc = launch_shade(alt, tab, 8 * tiles, ss, h->sv, a, pb, b - 1, &et))) return rc;
                 timed_end(h, ss, kinds, 2);
             }
         }

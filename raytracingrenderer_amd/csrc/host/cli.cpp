@@ -24,6 +24,9 @@
 // (none: every sample through the pixel centre, the reference's renderTile), -filterRadius r (pixels;
 // default 0.5 for box, 1 for tent), -lensRadius R (0: pinhole) and -focalDistance f, for one device
 // and for -gpus / -devices alike.
+// Environment light sampling (rtg_set_env_sampling): -envSampling uniform|luminance (uniform: the
+// reference's EnvironmentMap::sample; luminance: NEE directions drawn in proportion to the map's
+// luminance through an alias table), for one device and for -gpus / -devices alike.
 // Multi-GPU (one node): -gpus N renders on devices 0..N-1, -devices a,b,... on a list. Rank r
 // renders the 32x32 tiles with (tile_x + tile_y) % N == r, and the film is assembled on the first
 // device from every device's own tiles (packed, one RCCL send per device, scattered) before it is
@@ -99,17 +102,22 @@ int main(int argc, char** argv) {
     cs.filter_radius = std::stof(get("-filterRadius", cs.filter == RTG_FILTER_TENT ? "1" : "0.5"));
     cs.lens_radius = std::stof(get("-lensRadius", "0"));
     cs.focal_distance = std::stof(get("-focalDistance", "1"));
+    const std::string es = get("-envSampling", "uniform");
+    if (es != "uniform" && es != "luminance") return die("-envSampling", "one of uniform, luminance");
+    const int env_mode = es == "luminance" ? RTG_ENV_LUMINANCE : RTG_ENV_UNIFORM;
     rtg_handle* rt = nullptr;
     rtg_group* grp = nullptr;
     if (devices.empty()) {
         if (rtg_create(device, rth_scene_desc(scene), &rt) != 0) return die("rtg_create", rtg_last_error());
         if (rtg_set_options(rt, max_depth, RTG_OPT_CULL, 0) != 0) return die("rtg_set_options", rtg_last_error());
         if (rtg_set_camera_sampling(rt, &cs) != 0) return die("rtg_set_camera_sampling", rtg_last_error());
+        if (rtg_set_env_sampling(rt, env_mode) != 0) return die("rtg_set_env_sampling", rtg_last_error());
     } else {
         if (rtg_group_create(devices.data(), (int)devices.size(), rth_scene_desc(scene), &grp) != 0)
             return die("rtg_group_create", rtg_last_error());
         if (rtg_group_set_options(grp, max_depth, RTG_OPT_CULL, 0) != 0) return die("rtg_group_set_options", rtg_last_error());
         if (rtg_group_set_camera_sampling(grp, &cs) != 0) return die("rtg_group_set_camera_sampling", rtg_last_error());
+        if (rtg_group_set_env_sampling(grp, env_mode) != 0) return die("rtg_group_set_env_sampling", rtg_last_error());
         std::printf("%d devices, own-tile film exchange by %s\n", (int)devices.size(),
                     rtg_group_uses_rccl(grp) ? "RCCL (ncclSend/ncclRecv)"
                     : devices.size() == 1    ? "none (one device)"

@@ -212,6 +212,19 @@ def _camera_sampling(filter, filter_radius, lens_radius, focal_distance):
     return N.rtg_camera_sampling(filter, float(filter_radius), float(lens_radius), float(focal_distance))
 
 
+ENV_SAMPLING = {"uniform": N.RTG_ENV_UNIFORM, "luminance": N.RTG_ENV_LUMINANCE}
+
+
+def _env_mode(mode):
+    """The RTG_ENV_* value of set_env_sampling's argument (a name of ENV_SAMPLING or a value; an
+    unknown value is the library's error)."""
+    if isinstance(mode, str):
+        if mode not in ENV_SAMPLING:
+            raise ValueError("unknown environment sampling %r (one of %s)" % (mode, ", ".join(ENV_SAMPLING)))
+        return ENV_SAMPLING[mode]
+    return int(mode)
+
+
 class RayTracer:
     """RayTracer (Renderer.h:31-899) backed by librtg on one GPU."""
 
@@ -275,6 +288,57 @@ class RayTracer:
                                                   self.seed if seed is None else seed, N.ptr(rays, C.c_float),
                                                   N.ptr(xy, C.c_float)), self._lib.rtg_last_error)
         return rays, xy
+
+    def set_env_sampling(self, mode="uniform"):
+        """How NEE samples the environment light (rtg_set_env_sampling). "uniform" (default):
+        EnvironmentMap::sample's uniform sphere, the reference's films bit for bit. "luminance":
+        directions drawn in proportion to the map's filtered luminance times sin theta through an
+        alias table (built on the first use, kept with the tracer): the same expectation with far
+        less noise under a map whose light sits in a sun or a window; it draws four numbers per
+        environment sample instead of two, so its films are not the uniform mode's. A scene without
+        an environment light, or a black map, keeps sampling uniformly. Applies to render(),
+        adaptiveRender() and the "path", "direct" and "direct_mis" integrators; not to lightTracer(),
+        instantRadiosity() or the denoiser's guides."""
+        _check(self._lib.rtg_set_env_sampling(self._h, _env_mode(mode)), self._lib.rtg_last_error)
+
+    def env_sampling(self):
+        """The current setting, "uniform" or "luminance"."""
+        m = C.c_int()
+        _check(self._lib.rtg_get_env_sampling(self._h, C.byref(m)), self._lib.rtg_last_error)
+        return {v: k for k, v in ENV_SAMPLING.items()}.get(m.value, m.value)
+
+    def env_table(self):
+        """The active alias table (rtg_env_table): a dict of "prob" (H, W) float32, "alias" (H, W)
+        uint32, "cellpdf_self" and "cellpdf_alias" (H, W) float32, "entries" (H * W, 4) uint32 (the
+        words as the kernel loads them), "weights" (H, W) float64 (the cell weights it was built from)
+        and "build_ms"; None when no table is active (uniform mode, no environment light, a black map)."""
+        w, h, ms = C.c_uint32(), C.c_uint32(), C.c_double()
+        _check(self._lib.rtg_env_table(self._h, C.byref(w), C.byref(h), None, C.byref(ms)), self._lib.rtg_last_error)
+        if w.value == 0 or h.value == 0:
+            return None
+        e = np.zeros((w.value * h.value, 4), np.float32)
+        _check(self._lib.rtg_env_table(self._h, C.byref(w), C.byref(h), N.ptr(e, C.c_float), None),
+               self._lib.rtg_last_error)
+        wt = np.zeros((h.value, w.value), np.float64)
+        _check(self._lib.rtg_env_weights(self._h, N.ptr(wt, C.c_double)), self._lib.rtg_last_error)
+        u = e.view(np.uint32)
+        shape = (h.value, w.value)
+        return {"prob": e[:, 0].reshape(shape).copy(), "alias": u[:, 1].reshape(shape).copy(),
+                "cellpdf_self": e[:, 2].reshape(shape).copy(), "cellpdf_alias": e[:, 3].reshape(shape).copy(),
+                "entries": u.copy(), "weights": wt, "build_ms": ms.value}
+
+    def env_samples(self, r0, d):
+        """The shading kernel's own environment sample (rtg_probe_env_samples) for scripted draws
+        r0 (n,) uint32 and d (n, 3) = d1, d2, d3 against the active table: (wi (n, 3), pdf (n,)),
+        pdf 0 where the sample is rejected."""
+        r = np.ascontiguousarray(r0, np.uint32).reshape(-1)
+        dd = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        if len(r) != len(dd):
+            raise ValueError("env_samples: r0 and d must have one length")
+        out = np.zeros((len(r), 4), np.float32)
+        _check(self._lib.rtg_probe_env_samples(self._h, N.ptr(r, C.c_uint32), N.ptr(dd, C.c_float), len(r),
+                                               N.ptr(out, C.c_float)), self._lib.rtg_last_error)
+        return out[:, :3].copy(), out[:, 3].copy()
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -474,6 +538,10 @@ class RayTracerGroup:
         """RayTracer.set_camera_sampling on every rank (rtg_group_set_camera_sampling)."""
         p = _camera_sampling(filter, filter_radius, lens_radius, focal_distance)
         _check(self._lib.rtg_group_set_camera_sampling(self._g, C.byref(p)), self._lib.rtg_last_error)
+
+    def set_env_sampling(self, mode="uniform"):
+        """RayTracer.set_env_sampling on every rank (rtg_group_set_env_sampling)."""
+        _check(self._lib.rtg_group_set_env_sampling(self._g, _env_mode(mode)), self._lib.rtg_last_error)
 
     def setup_ms(self):
         """(host build of the device records, parallel uploads) of rtg_group_create, in ms."""

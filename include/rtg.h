@@ -274,7 +274,16 @@ int  rtg_probe_camera_samples(rtg_handle* h, const uint32_t* pixels, const uint3
  *                  EnvironmentMap::evaluate(wi), and the shadow ray and Ld = f E g / (pmf pdf) stay as
  *                  they are (pmf = 1 / n_lights: no power-weighted light selection, no MIS with
  *                  BSDF-sampled environment hits).
- *   unevenness     the integer cell pick gives each entry floor or ceil of 2^32 / N of the 2^32 values of
+ *   DIRECT_MIS     computeDirectMIS keeps its structure (Renderer.h:474-557): pdf is the one variable
+ *                  the light sample sets and the BSDF half reads. A visible environment sample returns
+ *                  f E g / (pmf pdf) at once, unweighted, as in uniform mode. Otherwise (rejected, g = 0
+ *                  or occluded) the BSDF sample follows with pdf as the sampler left it: the table's
+ *                  cp / st, or 0 after a rejected sample. A BSDF-sampled emitter hit then weights its
+ *                  area light with balance(pdf_b, (pdf pmf) dist^2 / cos), i.e. with the environment
+ *                  sample's pdf in the place of an area pdf: per-sample here where uniform mode has
+ *                  the constant 1 / (4 pi), and weight 1 after a rejected sample. The quirk is the
+ *                  reference's (it reuses the variable), inherited and not designed.
+ *   unevenness    the integer cell pick gives each entry floor or ceil of 2^32 / N of the 2^32 values of
  *                  r0: uneven by at most N / 2^32 relative (under 0.05 % for a 2048 x 1024 map).
  * A scene without an environment light, or a map whose weights sum to 0, accepts the mode and keeps
  * sampling uniformly, with the launches it has today. W * H > RTG_ENV_MAX_CELLS: RTG_ERR_ARG

@@ -41,6 +41,14 @@ def lib(flavour="rtm"):
         L.or_trace_closest.argtypes = [vp, f32p, C.c_uint32, f32p]
         L.or_trace_visible.argtypes = [vp, f32p, C.c_uint32, i32p]
         L.or_camera_rays.argtypes = [vp, u32p, C.c_uint32, f32p]
+        L.or_camera_sample_rays.restype = C.c_int
+        L.or_camera_sample_rays.argtypes = [vp, u32p, u32p, C.c_uint32, C.c_uint64, f32p, f32p]
+        L.or_set_camera_sampling.restype = C.c_int
+        L.or_set_camera_sampling.argtypes = [vp, C.c_int, C.c_float, C.c_float, C.c_float]
+        L.or_set_env_table.restype = C.c_int
+        L.or_set_env_table.argtypes = [vp, u32p, C.c_uint32, C.c_uint32]
+        L.or_env_counts.restype = C.c_int
+        L.or_env_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
         for fn in ("or_acosf", "or_sinf", "or_cosf"):
             getattr(L, fn).restype = C.c_float
             getattr(L, fn).argtypes = [C.c_float]
@@ -72,6 +80,35 @@ class Oracle:
         if getattr(self, "h", None):
             self.L.or_destroy(self.h)
             self.h = None
+
+    FILTERS = {"none": 0, "box": 1, "tent": 2}
+    ENV_COUNTS = ("samples", "rejected", "occluded", "paths_two", "mis_emitter", "mis_emitter_rejected")
+
+    def set_camera_sampling(self, filter="none", filter_radius=None, lens_radius=0.0, focal_distance=1.0):
+        """rtg_set_camera_sampling for render, render_adaptive, trace_paths and path_events (the light
+        tracer and instant radiosity keep the pixel-centre pinhole camera). filter_radius None: the
+        filter's default (box 0.5, tent 1)."""
+        f = self.FILTERS[filter] if isinstance(filter, str) else int(filter)
+        if filter_radius is None:
+            filter_radius = 1.0 if f == 2 else 0.5
+        if self.L.or_set_camera_sampling(self.h, f, filter_radius, lens_radius, focal_distance) != 0:
+            raise ValueError("or_set_camera_sampling: bad argument")
+
+    def set_env_table(self, entries, w=0, h=0):
+        """RTG_ENV_LUMINANCE with the alias table `entries` ((w*h, 4) uint32 words: prob, alias,
+        cellpdf_self, cellpdf_alias) of a w x h environment map; None: uniform sampling again."""
+        if entries is None:
+            self.L.or_set_env_table(self.h, None, 0, 0)
+            return
+        e = np.ascontiguousarray(entries, np.uint32).reshape(-1, 4)
+        if len(e) != w * h or self.L.or_set_env_table(self.h, _p(e, C.c_uint32), w, h) != 0:
+            raise ValueError("or_set_env_table: bad argument")
+
+    def env_counts(self, reset=True):
+        """{name: count} of what the luminance-mode environment samples met since the last reset."""
+        out = np.zeros(len(self.ENV_COUNTS), np.uint64)
+        self.L.or_env_counts(self.h, _p(out, C.c_uint64), 1 if reset else 0)
+        return dict(zip(self.ENV_COUNTS, (int(v) for v in out)))
 
     def render(self, n_samples, first=0, seed=1234, tiles=None, threads=1, film=None, count=False):
         if film is None:
@@ -132,7 +169,7 @@ class Oracle:
 
     EVENT_KINDS = {1: "closest hit (id, t, alpha, beta)", 2: "light sample (index, point/direction)",
                    3: "shadow ray (visible, maxT)", 4: "russian roulette (draw, probability, depth)",
-                   5: "BSDF sample (wi, pdf)"}
+                   5: "BSDF sample (wi, pdf)", 6: "luminance-mode environment sample (pdf, accepted)"}
 
     def path_events(self, pixel, sample, seed=1234, cap=256):
         """Event list of one path (or_path_events): (events[n, 5], radiance[3])."""
@@ -155,8 +192,17 @@ class Oracle:
         self.L.or_trace_visible(self.h, _p(r, C.c_float), len(r), _p(out, C.c_int32))
         return out
 
-    def camera_rays(self, pixels):
+    def camera_rays(self, pixels, samples=None, seed=1234):
+        """Pixel-centre camera rays (n, 6); with `samples`, the rays of those samples under the camera
+        sampling setting and their film positions: ((n, 6), (n, 2))."""
         p = np.ascontiguousarray(pixels, np.uint32)
         out = np.zeros((len(p), 6), np.float32)
-        self.L.or_camera_rays(self.h, _p(p, C.c_uint32), len(p), _p(out, C.c_float))
-        return out
+        if samples is None:
+            self.L.or_camera_rays(self.h, _p(p, C.c_uint32), len(p), _p(out, C.c_float))
+            return out
+        s = np.ascontiguousarray(samples, np.uint32)
+        xy = np.zeros((len(p), 2), np.float32)
+        if len(s) != len(p) or self.L.or_camera_sample_rays(self.h, _p(p, C.c_uint32), _p(s, C.c_uint32), len(p),
+                                                            seed, _p(out, C.c_float), _p(xy, C.c_float)) != 0:
+            raise ValueError("or_camera_sample_rays: bad argument")
+        return out, xy

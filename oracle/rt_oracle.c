@@ -23,6 +23,12 @@
  * on the flattened Scene of include/rtg.h (the host front-end's output), with the deterministic
  * PCG32 sampler of SURVEY.md Appendix B injected in place of MTRandom (Sampling.h:13-26).
  *
+ * The two opt-in sampling modes of include/rtg.h, which the reference does not have, are restated from
+ * that header's definition (not from the device code): or_set_camera_sampling (pixel-filter jitter and
+ * the thin lens, a camera ray per sample) and or_set_env_table (RTG_ENV_LUMINANCE: the environment
+ * branches of computeDirect and computeDirectMIS sample a caller-given alias table). Unset, every
+ * function below is the reference's.
+ *
  * Argument-evaluation order: the reference writes cosineSampleHemisphere(sampler.next(),
  * sampler.next()) (Materials.h:129) and uniformSampleSphere(sampler.next(), sampler.next())
  * (Lights.h:145); g++ evaluates those arguments right to left, so the FIRST draw becomes r2.
@@ -149,7 +155,17 @@ struct or_scene {
     rtg_camera cam;
     rtg_camera_proj proj;
     int W, H;
+    rtg_camera_sampling cs;  /* or_set_camera_sampling (default: RTG_FILTER_NONE, no lens) */
+    uint32_t* env_tab;       /* or_set_env_table: env_w * env_h entries of 4 words, or NULL (uniform) */
+    uint32_t env_w, env_h;
+    uint64_t* env_cnt;       /* or_env_counts: what the luminance-mode samples met (OR_ENV_*) */
 };
+
+/* Counters of the luminance-mode environment samples (or_env_counts), so that a test can assert that a
+ * film it compares holds the cases it is about. They are touched only while a table is set. */
+enum { OR_ENV_SAMPLES, OR_ENV_REJECTED, OR_ENV_OCCLUDED, OR_ENV_PATHS_TWO, OR_ENV_MIS_EMITTER, OR_ENV_MIS_EMITTER_REJ, OR_ENV_NCOUNT };
+static __thread int g_path_env; /* environment samples of the current path */
+static void env_count(const struct or_scene* s, int what) { __sync_fetch_and_add(&s->env_cnt[what], (uint64_t)1); }
 
 typedef struct {
     uint64_t ext_rays, shadow_rays, nodes, tris;
@@ -359,6 +375,57 @@ static Col bsdf_eval(const struct or_scene* s, const Shading* sd) {
     return cdivs(tex_sample(s, sd->bsdf->texture, sd->tu, sd->tv), (float)O_PI);
 }
 
+#if ORACLE_LIBM
+#define O_SINCOSF(x, s, c) (*(s) = sinf(x), *(c) = cosf(x))
+#else
+#define O_SINCOSF(x, s, c) rtm_sincosf(x, s, c)
+#endif
+
+/* RTG_ENV_LUMINANCE's sample (include/rtg.h, "sample"): the cell from the alias table by r0 and d1, the
+ * point in the cell by d2 and d3, wi and pdf = cellpdf / sin theta. Returns 0 with pdf = 0 for a
+ * rejected sample (!(st > 0) or !(pdf > 0)). */
+static int env_sample_table(const struct or_scene* s, uint32_t r0, float d1, float d2, float d3, V3* wi, float* pdf) {
+    uint32_t W = s->env_w, H = s->env_h, N = W * H;
+    uint32_t k = (uint32_t)(((uint64_t)r0 * N) >> 32);
+    const uint32_t* e = s->env_tab + (size_t)k * 4;
+    float prob, cp_self, cp_alias;
+    memcpy(&prob, &e[0], 4);
+    memcpy(&cp_self, &e[2], 4);
+    memcpy(&cp_alias, &e[3], 4);
+    int keep = d1 < prob;
+    uint32_t c = keep ? k : e[1];
+    float cp = keep ? cp_self : cp_alias;
+    uint32_t cx = c % W, cy = c / W;
+    float u = ((float)cx + d2) / (float)W;
+    float v = ((float)cy + d3) / (float)H;
+    float theta = 3.14159265f * v;
+    float phi = 6.2831855f * u;
+    float st, ct, sp, cph;
+    O_SINCOSF(theta, &st, &ct);
+    O_SINCOSF(phi, &sp, &cph);
+    *wi = v3(st * cph, ct, st * sp);
+    *pdf = cp / st;
+    if (!(st > 0) || !(*pdf > 0)) {
+        *pdf = 0.0f;
+        return 0;
+    }
+    return 1;
+}
+/* The four draws of the luminance-mode environment branch, in the header's order, and the sample. */
+static int env_light_sample(const struct or_scene* s, Pcg* smp, int li, V3* wi, float* pdf) {
+    uint32_t r0 = pcg_u32(smp);
+    float d1 = pcg_next(smp);
+    float d2 = pcg_next(smp);
+    float d3 = pcg_next(smp);
+    int ok = env_sample_table(s, r0, d1, d2, d3, wi, pdf);
+    ev_push(2, (float)li, wi->x, wi->y, wi->z); /* environment sample direction */
+    ev_push(6, *pdf, (float)ok, 0, 0);          /* its pdf (0: rejected) */
+    env_count(s, OR_ENV_SAMPLES);
+    if (!ok) env_count(s, OR_ENV_REJECTED);
+    if (++g_path_env == 2) env_count(s, OR_ENV_PATHS_TWO);
+    return ok;
+}
+
 /* RayTracer::computeDirect (Renderer.h:423-473) */
 static Col compute_direct(const struct or_scene* s, const Shading* sd, Pcg* smp, Counts* c) {
     if (is_spec(sd->bsdf)) return col(0.0f, 0.0f, 0.0f);
@@ -386,6 +453,18 @@ static Col compute_direct(const struct or_scene* s, const Shading* sd, Pcg* smp,
         if (G > 0) {
             if (scene_visible(s, sd->x, p, c))
                 return cdivs(cmuls(cmul(bsdf_eval(s, sd), emitted), G), pmf * pdf);
+        }
+    } else if (s->env_tab) { /* RTG_ENV_LUMINANCE (include/rtg.h): a rejected sample casts no shadow ray */
+        V3 wi;
+        float pdf;
+        if (env_light_sample(s, smp, li, &wi, &pdf)) {
+            Col emitted = env_eval(s, wi);
+            float G = win_max(vdot(wi, sd->sN), 0.0f);
+            if (G > 0) {
+                if (scene_visible(s, sd->x, vadd(sd->x, vmuls(wi, 10000.0f)), c))
+                    return cdivs(cmuls(cmul(bsdf_eval(s, sd), emitted), G), pmf * pdf);
+                env_count(s, OR_ENV_OCCLUDED);
+            }
         }
     } else { /* EnvironmentMap::sample */
         float q2 = pcg_next(smp);
@@ -465,6 +544,7 @@ static Col compute_direct_mis(const struct or_scene* s, const Shading* sd, Pcg* 
     if (s->nlight - 1 < li) li = s->nlight - 1;
     int lt = s->light[li];
     float pdf;
+    int env_sampled = 0;
     if (lt >= 0) {
         const Tri* T = &s->tri[lt];
         float r1 = pcg_next(smp);
@@ -492,6 +572,20 @@ static Col compute_direct_mis(const struct or_scene* s, const Shading* sd, Pcg* 
                 result = cadd(result, cdivs(cmuls(cmuls(cmul(bsdf_eval(s, sd), emitted), G), w), pmf * pdf));
             }
         }
+    } else if (s->env_tab) {
+        /* RTG_ENV_LUMINANCE: pdf is the table's (0 for a rejected sample), and the BSDF half below
+         * reads it as it reads the uniform one (include/rtg.h, "DIRECT_MIS") */
+        V3 wi;
+        env_sampled = 1;
+        if (env_light_sample(s, smp, li, &wi, &pdf)) {
+            Col emitted = env_eval(s, wi);
+            float G = win_max(vdot(wi, sd->sN), 0.0f);
+            if (G > 0) {
+                if (scene_visible(s, sd->x, vadd(sd->x, vmuls(wi, 10000.0f)), c))
+                    return cdivs(cmuls(cmul(bsdf_eval(s, sd), emitted), G), pmf * pdf);
+                env_count(s, OR_ENV_OCCLUDED);
+            }
+        }
     } else {
         float q2 = pcg_next(smp);
         float q1 = pcg_next(smp);
@@ -514,6 +608,10 @@ static Col compute_direct_mis(const struct or_scene* s, const Shading* sd, Pcg* 
         if (is_light(sl.bsdf)) {
             const float* e = sl.bsdf->emission;
             Col emitted2 = col(e[0], e[1], e[2]);
+            if (env_sampled) {
+                env_count(s, OR_ENV_MIS_EMITTER);
+                if (!(pdf > 0)) env_count(s, OR_ENV_MIS_EMITTER_REJ);
+            }
             V3 wi = vsub(sl.x, sd->x);
             float dist2 = vlen2(wi);
             wi = vnorm(wi);
@@ -574,6 +672,45 @@ static Ray camera_ray(const struct or_scene* s, float x, float y) {
     return ray_make(v3(c->origin[0], c->origin[1], c->origin[2]), d);
 }
 
+/* rtg_set_camera_sampling's filter offset of draw u (include/rtg.h) */
+static float filter_offset(int filter, float r, float u) {
+    if (filter == RTG_FILTER_BOX) return (u * 2.0f - 1.0f) * r;
+    if (filter == RTG_FILTER_TENT) {
+        float t = u < 0.5f ? sqrtf(2.0f * u) - 1.0f : 1.0f - sqrtf(2.0f - 2.0f * u);
+        return t * r;
+    }
+    return 0.0f;
+}
+static int camera_per_sample(const struct or_scene* s) { return s->cs.filter != RTG_FILTER_NONE || s->cs.lens_radius > 0.0f; }
+/* The camera ray of sample `sample` of pixel `pixel` under the camera sampling setting (include/rtg.h):
+ * four draws from the camera's own stream, always all four; the film position goes to fxy (or NULL). */
+static Ray camera_ray_sampled(const struct or_scene* s, uint32_t pixel, uint32_t sample, uint64_t seed, float* fxy) {
+    uint32_t x = pixel % (uint32_t)s->W, y = pixel / (uint32_t)s->W;
+    Pcg cs;
+    pcg_init(&cs, seed ^ 0x9E3779B97F4A7C15ULL, ((uint64_t)pixel << 16) | sample);
+    float u0 = pcg_next(&cs);
+    float u1 = pcg_next(&cs);
+    float u2 = pcg_next(&cs);
+    float u3 = pcg_next(&cs);
+    float px = ((float)x + 0.5f) + filter_offset(s->cs.filter, s->cs.filter_radius, u0);
+    float py = ((float)y + 0.5f) + filter_offset(s->cs.filter, s->cs.filter_radius, u1);
+    if (fxy) { fxy[0] = px; fxy[1] = py; }
+    Ray r = camera_ray(s, px, py);
+    float R = s->cs.lens_radius;
+    if (R > 0.0f) {
+        const float* k = s->cam.camera;
+        V3 xc = v3(k[0], k[4], k[8]), yc = v3(k[1], k[5], k[9]), zc = v3(k[2], k[6], k[10]);
+        float ft = s->cs.focal_distance / fabsf(vdot(r.dir, zc));
+        V3 P = vadd(r.o, vmuls(r.dir, ft));
+        float rr = R * sqrtf(u2);
+        float sn, cs_;
+        O_SINCOSF(6.2831855f * u3, &sn, &cs_);
+        V3 o = vadd(vadd(r.o, vmuls(xc, rr * cs_)), vmuls(yc, rr * sn));
+        r = ray_make(o, vnorm(vsub(P, o)));
+    }
+    return r;
+}
+
 /* RayTracer::direct (Renderer.h:393-407): emission or one NEE sample at the first hit; 0 on a miss */
 static Col direct_only(const struct or_scene* s, Ray* r, Pcg* smp, Counts* c) {
     Isect is = scene_traverse(s, r, c);
@@ -625,8 +762,9 @@ static Col pixel_sample(const struct or_scene* s, uint32_t pixel, uint32_t sampl
     uint32_t x = pixel % (uint32_t)s->W, y = pixel / (uint32_t)s->W;
     Pcg smp;
     pcg_init(&smp, seed, ((uint64_t)pixel << 16) | sample);
-    Ray r = camera_ray(s, x + 0.5f, y + 0.5f);
+    Ray r = camera_per_sample(s) ? camera_ray_sampled(s, pixel, sample, seed, NULL) : camera_ray(s, x + 0.5f, y + 0.5f);
     Col thr = col(1.0f, 1.0f, 1.0f);
+    g_path_env = 0;
     switch (s->integrator) {
     case RTG_INTEGRATOR_DIRECT: return direct_only(s, &r, &smp, c);
     case RTG_INTEGRATOR_ALBEDO: return albedo_only(s, &r, c);
@@ -718,16 +856,59 @@ or_scene* or_create(const rtg_scene_desc* d, int max_depth) {
     }
     s->light = (int*)calloc((size_t)d->n_lights + 1, sizeof(int));
     memcpy(s->light, d->lights, d->n_lights * sizeof(int));
+    s->cs.filter = RTG_FILTER_NONE; s->cs.filter_radius = 0.5f; s->cs.lens_radius = 0.0f; s->cs.focal_distance = 1.0f;
+    s->env_cnt = (uint64_t*)calloc(OR_ENV_NCOUNT, sizeof(uint64_t));
     return s;
 }
 
 void or_destroy(or_scene* s) {
     if (!s) return;
-    free(s->tri); free(s->node); free(s->mat); free(s->tex); free(s->texels); free(s->light); free(s);
+    free(s->tri); free(s->node); free(s->mat); free(s->tex); free(s->texels); free(s->light); free(s->env_tab); free(s->env_cnt); free(s);
 }
 
 void or_set_max_depth(or_scene* s, int max_depth) { if (s) s->max_depth = max_depth; }
 void or_set_integrator(or_scene* s, int integrator) { if (s) s->integrator = integrator; }
+
+/* rtg_set_camera_sampling (include/rtg.h) for pixel_sample: or_render, or_render_adaptive, or_trace_paths
+ * and or_path_events. The light tracer and instant radiosity keep the pixel-centre pinhole camera. */
+int or_set_camera_sampling(or_scene* s, int filter, float filter_radius, float lens_radius, float focal_distance) {
+    if (!s || filter < RTG_FILTER_NONE || filter > RTG_FILTER_TENT) return -1;
+    if (!(filter_radius >= 0.0f && filter_radius <= RTG_FILTER_MAX_RADIUS) || !(lens_radius >= 0.0f) || !isfinite(lens_radius)) return -1;
+    if (lens_radius > 0.0f && (!(focal_distance > 0.0f) || !isfinite(focal_distance))) return -1;
+    s->cs.filter = filter; s->cs.filter_radius = filter_radius; s->cs.lens_radius = lens_radius; s->cs.focal_distance = focal_distance;
+    return 0;
+}
+
+/* RTG_ENV_LUMINANCE (include/rtg.h): the alias table the environment branch of computeDirect and
+ * computeDirectMIS samples from, W * H entries {prob, alias, cellpdf_self, cellpdf_alias} as 32-bit
+ * words (copied). The table is an input: the caller builds it from the map. NULL: uniform again. */
+int or_set_env_table(or_scene* s, const uint32_t* entries, uint32_t W, uint32_t H) {
+    if (!s) return -1;
+    free(s->env_tab);
+    s->env_tab = NULL;
+    s->env_w = s->env_h = 0;
+    if (!entries) return 0;
+    if (s->env_tex < 0 || W == 0 || H == 0 || (uint64_t)W * H > RTG_ENV_MAX_CELLS) return -1;
+    size_t n = (size_t)W * H;
+    for (size_t i = 0; i < n; ++i)
+        if (entries[4 * i + 1] >= n) return -1;
+    s->env_tab = (uint32_t*)malloc(n * 16);
+    memcpy(s->env_tab, entries, n * 16);
+    s->env_w = W; s->env_h = H;
+    return 0;
+}
+
+/* What the luminance-mode environment samples met since the last reset: out[6] = samples drawn,
+ * rejected, accepted with g > 0 and occluded, paths with two or more samples, DIRECT_MIS BSDF samples
+ * that hit an emitter after an environment sample, and those after a rejected one (pdf 0). */
+int or_env_counts(or_scene* s, uint64_t* out, int reset) {
+    if (!s) return -1;
+    for (int i = 0; i < OR_ENV_NCOUNT; ++i) {
+        if (out) out[i] = s->env_cnt[i];
+        if (reset) s->env_cnt[i] = 0;
+    }
+    return 0;
+}
 
 /* Per-path radiance for an explicit (pixel, sample) list: out n*3. */
 int or_trace_paths(or_scene* s, const uint32_t* pixels, const uint32_t* samples, uint32_t n, uint64_t seed, float* out) {
@@ -741,7 +922,8 @@ int or_trace_paths(or_scene* s, const uint32_t* pixels, const uint32_t* samples,
 
 /* Event log of one path (pixel, sample): up to cap events of 5 floats {kind, a, b, c, d}:
  * 1 closest hit {id, t, alpha, beta}, 2 light sample {index, point or direction}, 3 shadow ray
- * {visible, maxT}, 4 Russian roulette {draw, probability, depth}, 5 BSDF sample {wi, pdf}.
+ * {visible, maxT}, 4 Russian roulette {draw, probability, depth}, 5 BSDF sample {wi, pdf}, 6 (after a
+ * luminance-mode environment sample's 2) {pdf, accepted}.
  * Returns the number of events (may exceed cap); radiance goes to L (3 floats). */
 int or_path_events(or_scene* s, uint32_t pixel, uint32_t sample, uint64_t seed, float* ev, int cap, float* L) {
     if (!s || s->nlight <= 0) return -1;
@@ -1125,6 +1307,19 @@ int or_camera_rays(or_scene* s, const uint32_t* pixels, uint32_t n, float* out) 
     for (uint32_t i = 0; i < n; ++i) {
         uint32_t x = pixels[i] % (uint32_t)s->W, y = pixels[i] / (uint32_t)s->W;
         Ray r = camera_ray(s, x + 0.5f, y + 0.5f);
+        out[i * 6] = r.o.x; out[i * 6 + 1] = r.o.y; out[i * 6 + 2] = r.o.z;
+        out[i * 6 + 3] = r.dir.x; out[i * 6 + 4] = r.dir.y; out[i * 6 + 5] = r.dir.z;
+    }
+    return 0;
+}
+
+/* Camera rays per (pixel, sample) under the camera sampling setting: out n*6 (o.xyz, dir.xyz),
+ * film_xy (or NULL) n*2 the film positions. */
+int or_camera_sample_rays(or_scene* s, const uint32_t* pixels, const uint32_t* samples, uint32_t n, uint64_t seed,
+                          float* out, float* film_xy) {
+    for (uint32_t i = 0; i < n; ++i) {
+        if (pixels[i] >= (uint32_t)(s->W * s->H)) return -1;
+        Ray r = camera_ray_sampled(s, pixels[i], samples[i], seed, film_xy ? film_xy + 2 * (size_t)i : NULL);
         out[i * 6] = r.o.x; out[i * 6 + 1] = r.o.y; out[i * 6 + 2] = r.o.z;
         out[i * 6 + 3] = r.dir.x; out[i * 6 + 4] = r.dir.y; out[i * 6 + 5] = r.dir.z;
     }

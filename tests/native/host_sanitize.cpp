@@ -30,6 +30,8 @@ or_scene* or_create(const rtg_scene_desc* d, int max_depth);
 void or_destroy(or_scene* s);
 int or_render(or_scene* s, uint32_t first, uint32_t n_samples, uint64_t seed, const uint32_t* tiles, uint32_t n_tiles,
               int threads, float* film, uint64_t* counts, int count);
+int or_set_camera_sampling(or_scene* s, int filter, float filter_radius, float lens_radius, float focal_distance);
+int or_set_env_table(or_scene* s, const uint32_t* entries, uint32_t W, uint32_t H);
 }
 
 namespace {
@@ -177,6 +179,25 @@ void load_and_render(const std::string& dir, int width, int height, bool render,
             std::vector<float> film((size_t)info.width * info.height * 3, 0.0f);
             uint64_t counts[5] = {0, 0, 0, 0, 0};
             if (or_render(os, 0, 1, 1234, nullptr, 0, 1, film.data(), counts, 1) != 0) g_fail = 1;
+            if (d->env_texture >= 0) {
+                // the oracle's opt-in sampling modes: tent + lens, and an alias table over the map's cells
+                // whose even entries keep their cell and whose odd ones defer to the last cell
+                const uint32_t tw = d->textures[d->env_texture].width, th = d->textures[d->env_texture].height;
+                const uint32_t n = tw * th;
+                const float one = 1.0f, cp = 0.05066059f;  // 1 / (2 pi^2)
+                std::vector<uint32_t> tab((size_t)n * 4);
+                for (uint32_t k = 0; k < n; ++k) {
+                    std::memcpy(&tab[4 * (size_t)k], &one, 4);
+                    if (k & 1) tab[4 * (size_t)k] = 0;
+                    tab[4 * (size_t)k + 1] = (k & 1) ? n - 1 : k;
+                    std::memcpy(&tab[4 * (size_t)k + 2], &cp, 4);
+                    std::memcpy(&tab[4 * (size_t)k + 3], &cp, 4);
+                }
+                if (or_set_env_table(os, tab.data(), tw, th) != 0) g_fail = 1;
+                if (or_set_camera_sampling(os, 2, 1.0f, 0.05f, 5.0f) != 0) g_fail = 1;
+                if (or_render(os, 1, 1, 1234, nullptr, 0, 2, film.data(), counts, 1) != 0) g_fail = 1;
+                if (or_set_env_table(os, nullptr, 0, 0) != 0) g_fail = 1;
+            }
             std::vector<uint8_t> rgb(film.size());
             rth_tonemap(info.width, info.height, film.data(), 1, 1.0f, rgb.data());
             or_destroy(os);

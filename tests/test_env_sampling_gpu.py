@@ -285,7 +285,8 @@ def test_both_modes_agree_in_expectation_and_luminance_is_less_noisy(tmp_path):
     8 seeds x 256 spp per mode. The image-mean luminances differ by at most six standard errors of
     the difference (from the spread across seeds), neither standard error exceeds 5 % of its mean
     (uniform side on the CPU oracle, same seeds: 0.8 %), and the spread across seeds is smaller in
-    luminance mode."""
+    luminance mode. (The exact comparison of luminance-mode PATH films, bit for bit against the C oracle,
+    lives in tests/test_sampling_modes_gpu.py; this test keeps the two modes' agreement and the gain.)"""
     s = loadScene(write_table_scene_with_map(tmp_path / "patch", patch_map(), 6, 4), width=32, height=24)
     assert (np.array(s.lights) == -1).sum() == 1 and len(s.lights) == 13
     means = {}

@@ -40,7 +40,7 @@ extern "C" {
  *    rtg_film_scatter takes the film's pixel count; rtg_stats.lane_idle_* appended
  *    (additive, still 6: the denoiser, rtg_denoise_* and rtg_group_denoise; camera sampling,
  *    rtg_*_camera_sampling and rtg_probe_camera_samples; environment light sampling,
- *    rtg_*_env_sampling, rtg_env_* and rtg_probe_env_samples) */
+ *    rtg_*_env_sampling, rtg_env_* and rtg_probe_env_samples; rtg_probe_connect) */
 #define RTG_ABI_VERSION 6
 
 /* error codes */
@@ -531,6 +531,15 @@ int  rtg_probe_math(int fn, const float* in, uint32_t n, float* out);
 #define RTG_PROBE_TEX_ENV     1
 #define RTG_PROBE_TEX_UNIFORM 2
 int  rtg_probe_texture(int mode, const float* texels_rgb, uint32_t w, uint32_t h, const float* in, uint32_t n,
+                       float* out);
+/* Camera-connection probe: the light tracer's own connectToCamera (Renderer.h:236-262) on the handle's
+ * camera, up to and apart from its visibility test, on n points. points, normals, colours: n*3 floats
+ * each (the vertex, its shading normal, the colour thr * f * Le to connect). out: n*12 floats per point:
+ * accepted (int32 1 / 0), the splat pixel y * width + x (int32), the splatted colour col * W_e * G (3),
+ * Scene::visible(p, camera.origin)'s ray origin (3) and maxT, its direction (3); all zero where the
+ * connection is not accepted (projectOntoCamera refuses the point, a cosine is negative, or the pixel
+ * lies off the film). n <= (2^31 - 1) / 12. */
+int  rtg_probe_connect(rtg_handle* h, const float* points, const float* normals, const float* colours, uint32_t n,
                        float* out);
 
 #ifdef __cplusplus

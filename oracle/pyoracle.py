@@ -30,9 +30,11 @@ def lib(flavour="rtm"):
         L.or_render_adaptive.restype = C.c_int
         L.or_render_adaptive.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p]
         L.or_render_light.restype = C.c_int
-        L.or_render_light.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, f32p]
+        L.or_render_light.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, f32p, C.POINTER(C.c_uint64)]
         L.or_render_ir.restype = C.c_int
-        L.or_render_ir.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, f32p]
+        L.or_render_ir.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, f32p, C.POINTER(C.c_uint64)]
+        L.or_connect_probe.restype = C.c_int
+        L.or_connect_probe.argtypes = [vp, f32p, f32p, f32p, C.c_uint32, f32p, f32p]
         L.or_camera_project.argtypes = [vp, f32p, C.c_uint32, f32p]
         L.or_light_emit.argtypes = [vp, C.c_int, f32p, f32p]
         L.or_trace_paths.argtypes = [vp, u32p, u32p, C.c_uint32, C.c_uint64, f32p]
@@ -133,19 +135,45 @@ class Oracle:
             raise RuntimeError("or_render_adaptive failed")
         return film, counts
 
-    def render_light(self, n_frames=1, first=0, seed=1234, film=None):
-        if film is None:
-            film = np.zeros((self.H, self.W, 3), np.float32)
-        if self.L.or_render_light(self.h, first, n_frames, seed, _p(film, C.c_float)) != 0:
-            raise RuntimeError("or_render_light failed")
-        return film
+    LIGHT_COUNTS = ("paths", "extension_rays", "shadow_rays", "splats", "off_film")
 
-    def render_instant_radiosity(self, n_frames=1, first=0, seed=1234, n_vpl=50, film=None):
+    def render_light(self, n_frames=1, first=0, seed=1234, film=None, count=False):
+        """The light tracer's film; with count, (film, {name: total}) over LIGHT_COUNTS: light paths,
+        Scene::traverse calls, Scene::visible calls, splats that landed in the film, and camera
+        connections whose shadow ray was cast although their pixel lies off the film."""
         if film is None:
             film = np.zeros((self.H, self.W, 3), np.float32)
-        if self.L.or_render_ir(self.h, first, n_frames, seed, n_vpl, _p(film, C.c_float)) != 0:
+        counts = np.zeros(len(self.LIGHT_COUNTS), np.uint64)
+        if self.L.or_render_light(self.h, first, n_frames, seed, _p(film, C.c_float), _p(counts, C.c_uint64)) != 0:
+            raise RuntimeError("or_render_light failed")
+        return (film, dict(zip(self.LIGHT_COUNTS, (int(v) for v in counts)))) if count else film
+
+    def render_instant_radiosity(self, n_frames=1, first=0, seed=1234, n_vpl=50, film=None, count=False):
+        """Instant radiosity's film; with count, (film, {name: total}) over LIGHT_COUNTS: VPL paths plus
+        one camera path per pixel, the Scene::traverse calls of both, computeVPLsContribution's
+        Scene::visible calls, and the pixels splatted (those whose camera ray hit)."""
+        if film is None:
+            film = np.zeros((self.H, self.W, 3), np.float32)
+        counts = np.zeros(len(self.LIGHT_COUNTS), np.uint64)
+        if self.L.or_render_ir(self.h, first, n_frames, seed, n_vpl, _p(film, C.c_float), _p(counts, C.c_uint64)) != 0:
             raise RuntimeError("or_render_ir failed")
-        return film
+        return (film, dict(zip(self.LIGHT_COUNTS, (int(v) for v in counts)))) if count else film
+
+    CONN_STAGES = {0: "accepted", 1: "rejected by projection", 2: "rejected by cosine", 3: "rejected by pixel bounds"}
+
+    def connect_probe(self, points, normals, colours):
+        """connectToCamera on n points apart from its visibility test (or_connect_probe): (out (n, 12)
+        float32 = accepted and pixel as int32 bits, colour, shadow-ray origin, maxT, direction, all zero
+        where not accepted; stage (n,) int, a key of CONN_STAGES; xy (n, 2) projectOntoCamera's outputs)."""
+        p, nn, c = (np.ascontiguousarray(v, np.float32).reshape(-1, 3) for v in (points, normals, colours))
+        if not len(p) == len(nn) == len(c):
+            raise ValueError("connect_probe: points, normals and colours must have one length")
+        out = np.zeros((len(p), 12), np.float32)
+        info = np.zeros((len(p), 3), np.float32)
+        if self.L.or_connect_probe(self.h, _p(p, C.c_float), _p(nn, C.c_float), _p(c, C.c_float), len(p),
+                                   _p(out, C.c_float), _p(info, C.c_float)) != 0:
+            raise ValueError("or_connect_probe: bad argument")
+        return out, info[:, 0].astype(np.int64), info[:, 1:].copy()
 
     def camera_project(self, pts):
         p = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)

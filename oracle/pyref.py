@@ -113,6 +113,16 @@ class RefScene:
         self.L.ref_camera_project(C.c_void_p(self.h), _p(p), len(p), _p(out), _p(state))
         return out, state
 
+    def connect_probe(self, points, normals, colours):
+        """RayTracer::connectToCamera without its visibility test on the reference's classes
+        (ref_connect_probe): (stage (n,) int as Oracle.CONN_STAGES, pixel (n,) int or -1, colour (n, 3),
+        xy (n, 2) projectOntoCamera's outputs)."""
+        p, nn, c = (np.ascontiguousarray(v, np.float32).reshape(-1, 3) for v in (points, normals, colours))
+        out = np.zeros((len(p), 8), np.float32)
+        self.L.ref_connect_probe.restype = None
+        self.L.ref_connect_probe(C.c_void_p(self.h), _p(p), _p(nn), _p(c), len(p), _p(out))
+        return out[:, 0].astype(np.int64), out[:, 1].astype(np.int64), out[:, 2:5].copy(), out[:, 5:7].copy()
+
     def light_emit(self, li, draws):
         d = np.ascontiguousarray(draws, np.float32)
         out = np.zeros(12, np.float32)

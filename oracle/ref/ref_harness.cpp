@@ -895,6 +895,50 @@ void ref_camera_project(void* h, const float* pts, int n, float* out, float* sta
     state[35] = c.Afilm;
 }
 
+// RayTracer::connectToCamera (Renderer.h:236-262) on n points (pts, nrm, col: n*3 each) without its
+// visibility test, on the reference's Camera, Vec3, Colour and Film. out n*8: stage (0 splatted, 1
+// projectOntoCamera refused, 2 a negative cosine, 3 Film::splat found the pixel off the film), the
+// pixel Film::splat added to (-1: none), the colour handed to it, projectOntoCamera's x and y.
+void ref_connect_probe(void* h, const float* pts, const float* nrm, const float* col, int n, float* out) {
+    Scene* scene = ((RefScene*)h)->scene;
+    const int W = (int)scene->camera.width, H = (int)scene->camera.height;
+    Film film;
+    film.init(W, H, new BoxFilter());
+    for (int i = 0; i < n; i++) {
+        float* o = out + (size_t)i * 8;
+        Vec3 p(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
+        Vec3 nn(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]);
+        Colour c(col[3 * i], col[3 * i + 1], col[3 * i + 2]);
+        float x = 0, y = 0;
+        o[0] = 1.0f; o[1] = -1.0f; o[2] = o[3] = o[4] = 0.0f;
+        const bool ok = scene->camera.projectOntoCamera(p, x, y);
+        o[5] = x; o[6] = y;
+        if (!ok) continue;
+        float A_film = scene->camera.Afilm;
+        Vec3 direction = scene->camera.origin - p;
+        float dist2 = direction.lengthSq();
+        direction = direction.normalize();
+        float cos_theta_shading = Dot(nn, direction);
+        float cos_theta_cam = Dot(scene->camera.viewDirection, -direction);
+        o[0] = 2.0f;
+        if (cos_theta_shading < 0.0f || cos_theta_cam < 0.0f) continue;
+        float G = (cos_theta_shading * cos_theta_cam) / dist2;
+        float W_e = 1 / (A_film * SQ(SQ(cos_theta_cam)));
+        Colour color = c * W_e * G;
+        o[2] = color.r; o[3] = color.g; o[4] = color.b;
+        // where Film::splat puts a colour: splat white into the cleared film and look for it
+        film.splat(x, y, Colour(1.0f, 1.0f, 1.0f));
+        o[0] = 3.0f;
+        for (int k = 0; k < W * H; k++)
+            if (film.film[k].r != 0.0f) {
+                o[0] = 0.0f;
+                o[1] = (float)k;
+                film.film[k] = Colour(0.0f, 0.0f, 0.0f);
+                break;
+            }
+    }
+}
+
 // AreaLight samplePositionFromLight + sampleDirectionFromLight + evaluate(-wi) (Lights.h:30-80) for
 // Scene::lights[li] with scripted draws: out = p.xyz, pdfPosition, wi.xyz, pdfDirection, Le.rgb,
 // draws used (lightTrace_init, Renderer.h:264-281).

@@ -271,12 +271,16 @@ static Isect scene_traverse(const struct or_scene* s, const Ray* r, Counts* c) {
     return is;
 }
 
-/* Scene::visible (Scene.h:161-169) */
-static int scene_visible(const struct or_scene* s, V3 p1, V3 p2, Counts* c) {
+/* Scene::visible (Scene.h:161-169): the shadow ray from p1 towards p2 and its maxT */
+static Ray visible_ray(V3 p1, V3 p2, float* maxT) {
     V3 dir = vsub(p2, p1);
-    float maxT = vlen(dir) - (2.0f * O_EPS);
+    *maxT = vlen(dir) - (2.0f * O_EPS);
     dir = vnorm(dir);
-    Ray r = ray_make(vadd(p1, vmuls(dir, O_EPS)), dir);
+    return ray_make(vadd(p1, vmuls(dir, O_EPS)), dir);
+}
+static int scene_visible(const struct or_scene* s, V3 p1, V3 p2, Counts* c) {
+    float maxT;
+    Ray r = visible_ray(p1, p2, &maxT);
     if (c) c->shadow_rays++;
     int vis = traverse_visible(s, 0, &r, maxT, c);
     ev_push(3, (float)vis, maxT, 0, 0); /* shadow ray */
@@ -1097,33 +1101,66 @@ static int project_onto_camera(const struct or_scene* s, V3 p, float* x, float* 
 }
 /* (int)x with x86-64 cvttss2si semantics (NaN / out of range -> INT_MIN) */
 static int trunc_x86(float x) { return (x >= -2147483648.0f && x < 2147483648.0f) ? (int)x : (int)0x80000000; }
-/* Film::splat, BoxFilter (size 0): film[(int)y * W + (int)x] += L * 1 / 1 (Imaging.h:209-232) */
-static void splat(const struct or_scene* s, float* film, float x, float y, Col L) {
+/* Film::splat, BoxFilter (size 0): film[(int)y * W + (int)x] += L * 1 / 1 (Imaging.h:209-232);
+ * the pixel index, or -1 off the film */
+static long splat_pixel(const struct or_scene* s, float x, float y) {
     int px = trunc_x86(x), py = trunc_x86(y);
-    if (px >= 0 && (unsigned)px < (unsigned)s->W && py >= 0 && (unsigned)py < (unsigned)s->H) {
-        float* f = film + ((size_t)py * (unsigned)s->W + (unsigned)px) * 3;
+    if (px >= 0 && (unsigned)px < (unsigned)s->W && py >= 0 && (unsigned)py < (unsigned)s->H)
+        return (long)((size_t)py * (unsigned)s->W + (unsigned)px);
+    return -1;
+}
+static void splat(const struct or_scene* s, float* film, float x, float y, Col L) {
+    long pix = splat_pixel(s, x, y);
+    if (pix >= 0) {
+        float* f = film + (size_t)pix * 3;
         f[0] = f[0] + ((L.r * 1.0f) / 1.0f);
         f[1] = f[1] + ((L.g * 1.0f) / 1.0f);
         f[2] = f[2] + ((L.b * 1.0f) / 1.0f);
     }
 }
-/* RayTracer::connectToCamera (Renderer.h:236-262) */
-static void connect_to_camera(const struct or_scene* s, V3 p, V3 n, Col c, float* film, Counts* cnt) {
-    float x, y;
-    if (project_onto_camera(s, p, &x, &y)) {
-        float A = s->proj.a_film;
-        V3 org = v3(s->cam.origin[0], s->cam.origin[1], s->cam.origin[2]);
-        V3 dir = vsub(org, p);
-        float dist2 = vlen2(dir);
-        dir = vnorm(dir);
-        float cs = vdot(n, dir);
-        float cc = vdot(v3(s->proj.view_direction[0], s->proj.view_direction[1], s->proj.view_direction[2]), vneg(dir));
-        if (cs < 0.0f || cc < 0.0f) return;
-        float G = (cs * cc) / dist2;
-        if (!scene_visible(s, p, org, cnt)) return;
-        float We = 1 / (A * ((cc * cc) * (cc * cc)));
-        splat(s, film, x, y, cmuls(cmuls(c, We), G));
-    }
+/* What the light-path drivers count (or_render_light, or_render_ir): LP_SPLATS the camera connections
+ * that added to a pixel of the film, LP_OFF_FILM those that passed the projection and cosine tests and
+ * whose pixel lies off the film (the reference casts their shadow ray all the same, before
+ * Film::splat drops them). */
+enum { LP_PATHS, LP_EXT_RAYS, LP_SHADOW_RAYS, LP_SPLATS, LP_OFF_FILM, LP_NCOUNT };
+typedef struct { Counts c; uint64_t splats, off_film; } LightCounts;
+/* RayTracer::connectToCamera (Renderer.h:236-262) apart from its visibility test. stage: CONN_OK the
+ * connection would splat `out` into `pixel` if p sees the camera; CONN_PROJECTION projectOntoCamera
+ * refused p; CONN_COSINE a cosine is negative; CONN_PIXEL Film::splat finds (x, y) off the film. x, y:
+ * projectOntoCamera's outputs (film coordinates where it accepts). */
+enum { CONN_OK, CONN_PROJECTION, CONN_COSINE, CONN_PIXEL };
+typedef struct { int stage; long pixel; float x, y; Col out; } Conn;
+static Conn connect_prepare(const struct or_scene* s, V3 p, V3 n, Col c) {
+    Conn k;
+    k.stage = CONN_PROJECTION;
+    k.pixel = -1;
+    k.out = col(0.0f, 0.0f, 0.0f);
+    k.x = k.y = 0.0f;
+    if (!project_onto_camera(s, p, &k.x, &k.y)) return k;
+    float A = s->proj.a_film;
+    V3 org = v3(s->cam.origin[0], s->cam.origin[1], s->cam.origin[2]);
+    V3 dir = vsub(org, p);
+    float dist2 = vlen2(dir);
+    dir = vnorm(dir);
+    float cs = vdot(n, dir);
+    float cc = vdot(v3(s->proj.view_direction[0], s->proj.view_direction[1], s->proj.view_direction[2]), vneg(dir));
+    k.stage = CONN_COSINE;
+    if (cs < 0.0f || cc < 0.0f) return k;
+    float G = (cs * cc) / dist2;
+    float We = 1 / (A * ((cc * cc) * (cc * cc)));
+    k.out = cmuls(cmuls(c, We), G);
+    k.pixel = splat_pixel(s, k.x, k.y);
+    k.stage = k.pixel < 0 ? CONN_PIXEL : CONN_OK;
+    return k;
+}
+static void connect_to_camera(const struct or_scene* s, V3 p, V3 n, Col c, float* film, LightCounts* cnt) {
+    Conn k = connect_prepare(s, p, n, c);
+    if (k.stage == CONN_PROJECTION || k.stage == CONN_COSINE) return;
+    if (cnt && k.stage == CONN_PIXEL) cnt->off_film++;
+    V3 org = v3(s->cam.origin[0], s->cam.origin[1], s->cam.origin[2]);
+    if (!scene_visible(s, p, org, cnt ? &cnt->c : NULL)) return;
+    if (cnt && k.stage == CONN_OK) cnt->splats++;
+    splat(s, film, k.x, k.y, k.out);
 }
 /* AreaLight: samplePositionFromLight (Triangle::sample) + sampleDirectionFromLight (Lights.h:63-80) */
 static void light_emit_sample(const struct or_scene* s, const Tri* T, Pcg* smp, V3* p, float* pdf_pos, V3* wi,
@@ -1145,9 +1182,9 @@ static void light_emit_sample(const struct or_scene* s, const Tri* T, Pcg* smp, 
     (void)s;
 }
 /* RayTracer::lightTracePath (Renderer.h:292-326) */
-static void light_trace_path(const struct or_scene* s, Ray* r, Col thr, Col Le, Pcg* smp, float* film, Counts* c) {
+static void light_trace_path(const struct or_scene* s, Ray* r, Col thr, Col Le, Pcg* smp, float* film, LightCounts* c) {
     for (;;) {
-        Isect is = scene_traverse(s, r, c);
+        Isect is = scene_traverse(s, r, c ? &c->c : NULL);
         Shading sd = shading_data(s, &is, r);
         if (!(sd.t < FLT_MAX)) return;
         if (is_light(sd.bsdf) || is_spec(sd.bsdf)) return;
@@ -1165,12 +1202,25 @@ static void light_trace_path(const struct or_scene* s, Ray* r, Col thr, Col Le, 
         (void)wi;
     }
 }
+static void light_counts_out(const LightCounts* lc, uint64_t* counts) {
+    if (!counts) return;
+    counts[LP_EXT_RAYS] += lc->c.ext_rays;
+    counts[LP_SHADOW_RAYS] += lc->c.shadow_rays;
+    counts[LP_SPLATS] += lc->splats;
+    counts[LP_OFF_FILM] += lc->off_film;
+}
 /* RayTracer::lightTracer + lightTrace_init (Renderer.h:221-235, 264-291): W*H light paths per frame,
- * path i drawing from the PCG stream keyed (seed, i, frame). */
-int or_render_light(or_scene* s, uint32_t first, uint32_t n_frames, uint64_t seed, float* film) {
+ * path i drawing from the PCG stream keyed (seed, i, frame). counts (or NULL): LP_NCOUNT totals of
+ * this call, added to what the array holds: light paths (W*H per frame, whichever light they draw),
+ * Scene::traverse calls, Scene::visible calls, splats that landed in the film, connections off the
+ * film. */
+int or_render_light(or_scene* s, uint32_t first, uint32_t n_frames, uint64_t seed, float* film, uint64_t* counts) {
     if (!s || !film || s->nlight <= 0) return -1;
+    LightCounts lc;
+    memset(&lc, 0, sizeof(lc));
     for (uint32_t f = first; f < first + n_frames; ++f) {
         for (uint32_t i = 0; i < (uint32_t)(s->W * s->H); ++i) {
+            if (counts) counts[LP_PATHS]++;
             Pcg smp;
             pcg_init(&smp, seed, ((uint64_t)i << 16) | f);
             float pmf = 1.f / (float)s->nlight;
@@ -1186,11 +1236,12 @@ int or_render_light(or_scene* s, uint32_t first, uint32_t n_frames, uint64_t see
             const float* e = s->mat[T->mat].emission;
             Col ev = vdot(vneg(wi), gn) < 0 ? col(e[0], e[1], e[2]) : col(0.0f, 0.0f, 0.0f); /* evaluate(-wi) */
             Col Le = cdivs(cmuls(ev, cos_t), (pmf * pdf_dir) * pdf_pos);
-            connect_to_camera(s, p, gn, Le, film, NULL);
+            connect_to_camera(s, p, gn, Le, film, &lc);
             Ray r = ray_make(p, wi);
-            light_trace_path(s, &r, col(1.0f, 1.0f, 1.0f), Le, &smp, film, NULL);
+            light_trace_path(s, &r, col(1.0f, 1.0f, 1.0f), Le, &smp, film, &lc);
         }
     }
+    light_counts_out(&lc, counts);
     return 0;
 }
 
@@ -1206,9 +1257,9 @@ static void vpl_push(VplList* l, V3 x, V3 n, Col Le) {
     l->n++;
 }
 /* RayTracer::VPLTracePath (Renderer.h:183-218, recursion unrolled) */
-static void vpl_trace_path(const struct or_scene* s, Ray* r, Col thr, Col Le, Pcg* smp, VplList* out) {
+static void vpl_trace_path(const struct or_scene* s, Ray* r, Col thr, Col Le, Pcg* smp, VplList* out, Counts* c) {
     for (;;) {
-        Isect is = scene_traverse(s, r, NULL);
+        Isect is = scene_traverse(s, r, c);
         Shading sd = shading_data(s, &is, r);
         if (!(sd.t < FLT_MAX)) return;
         if (!is_light(sd.bsdf) && !is_spec(sd.bsdf))
@@ -1224,11 +1275,17 @@ static void vpl_trace_path(const struct or_scene* s, Ray* r, Col thr, Col Le, Pc
     }
 }
 /* RayTracer::instantRadiosity: traceVPLs (n_vpl paths, path i keyed (seed, i, frame)), then per pixel
- * the first hit and computeVPLsContribution (Renderer.h:101-156). */
-int or_render_ir(or_scene* s, uint32_t first, uint32_t n_frames, uint64_t seed, uint32_t n_vpl, float* film) {
+ * the first hit and computeVPLsContribution (Renderer.h:101-156). counts (or NULL): as or_render_light;
+ * paths are the n_vpl VPL paths plus one camera path per pixel, per frame, Scene::traverse calls those of
+ * both, Scene::visible calls those of computeVPLsContribution, splats the pixels whose camera ray hit. */
+int or_render_ir(or_scene* s, uint32_t first, uint32_t n_frames, uint64_t seed, uint32_t n_vpl, float* film,
+                 uint64_t* counts) {
     if (!s || !film || s->nlight <= 0 || n_vpl == 0) return -1;
+    LightCounts lc;
+    memset(&lc, 0, sizeof(lc));
     for (uint32_t f = first; f < first + n_frames; ++f) {
         VplList vl = {NULL, 0, 0};
+        if (counts) counts[LP_PATHS] += (uint64_t)n_vpl + (uint64_t)s->W * (uint64_t)s->H;
         for (uint32_t i = 0; i < n_vpl; ++i) {
             Pcg smp;
             pcg_init(&smp, seed, ((uint64_t)i << 16) | f);
@@ -1247,12 +1304,12 @@ int or_render_ir(or_scene* s, uint32_t first, uint32_t n_frames, uint64_t seed, 
             vpl_push(&vl, p, gn, cdivs(ev, den));
             Col Le = cdivs(cmuls(ev, vdot(wi, gn)), den);
             Ray r = ray_make(p, wi);
-            vpl_trace_path(s, &r, col(1.0f, 1.0f, 1.0f), Le, &smp, &vl);
+            vpl_trace_path(s, &r, col(1.0f, 1.0f, 1.0f), Le, &smp, &vl, &lc.c);
         }
         for (uint32_t y = 0; y < (uint32_t)s->H; ++y)
             for (uint32_t x = 0; x < (uint32_t)s->W; ++x) {
                 Ray r = camera_ray(s, x + 0.5f, y + 0.5f);
-                Isect is = scene_traverse(s, &r, NULL);
+                Isect is = scene_traverse(s, &r, &lc.c);
                 Shading sd = shading_data(s, &is, &r);
                 if (!(sd.t < FLT_MAX)) continue;
                 Col sum = col(0.0f, 0.0f, 0.0f);
@@ -1266,14 +1323,16 @@ int or_render_ir(or_scene* s, uint32_t first, uint32_t n_frames, uint64_t seed, 
                         float cx = vdot(sd.sN, dir);
                         if (cv <= 0.0f || cx <= 0.0f) continue;
                         float G = (cv * cx) / dist2;
-                        if (!scene_visible(s, sd.x, vl.v[j].x, NULL)) continue;
+                        if (!scene_visible(s, sd.x, vl.v[j].x, &lc.c)) continue;
                         sum = cadd(sum, cmuls(cmul(vl.v[j].Le, bsdf_eval(s, &sd)), G));
                     }
                 }
+                lc.splats++;
                 splat(s, film, x + 0.5f, y + 0.5f, sum);
             }
         free(vl.v);
     }
+    light_counts_out(&lc, counts);
     return 0;
 }
 
@@ -1334,6 +1393,33 @@ int or_camera_project(or_scene* s, const float* pts, uint32_t n, float* out) {
         float x = 0, y = 0;
         int ok = project_onto_camera(s, v3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]), &x, &y);
         out[3 * i] = ok ? 1.0f : 0.0f; out[3 * i + 1] = x; out[3 * i + 2] = y;
+    }
+    return 0;
+}
+/* connectToCamera on n points (pts, nrm, col: n*3 each) up to and apart from its visibility test.
+ * out n*12: stage == CONN_OK as an int (1 accepted, 0 not), the splat pixel as an int, the splatted
+ * colour (3), Scene::visible's ray origin (3) and maxT, its direction (3); all zero where not
+ * accepted. info n*3 (or NULL): the stage (CONN_*) as a float, and projectOntoCamera's x, y. */
+int or_connect_probe(or_scene* s, const float* pts, const float* nrm, const float* colr, uint32_t n, float* out,
+                     float* info) {
+    if (!s || !pts || !nrm || !colr || !out) return -1;
+    V3 org = v3(s->cam.origin[0], s->cam.origin[1], s->cam.origin[2]);
+    for (uint32_t i = 0; i < n; ++i) {
+        V3 p = v3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
+        Conn k = connect_prepare(s, p, v3(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]),
+                                 col(colr[3 * i], colr[3 * i + 1], colr[3 * i + 2]));
+        float* o = out + (size_t)i * 12;
+        memset(o, 0, 12 * sizeof(float));
+        if (info) { info[3 * i] = (float)k.stage; info[3 * i + 1] = k.x; info[3 * i + 2] = k.y; }
+        if (k.stage != CONN_OK) continue;
+        int32_t one = 1, pix = (int32_t)k.pixel;
+        float maxT;
+        Ray r = visible_ray(p, org, &maxT);
+        memcpy(o, &one, 4);
+        memcpy(o + 1, &pix, 4);
+        o[2] = k.out.r; o[3] = k.out.g; o[4] = k.out.b;
+        o[5] = r.o.x; o[6] = r.o.y; o[7] = r.o.z; o[8] = maxT;
+        o[9] = r.dir.x; o[10] = r.dir.y; o[11] = r.dir.z;
     }
     return 0;
 }

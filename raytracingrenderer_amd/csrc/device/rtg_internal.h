@@ -244,6 +244,7 @@ struct RoctxRange {
         hipError_t e_ = (expr);                                                              \
         if (e_ != hipSuccess) {                                                              \
             g_err = std::string(#expr) + ": " + hipGetErrorString(e_);                       \
+            (void)hipGetLastError(); /* reported here: a later LAUNCH_OK must not find it */ \
             return RTG_ERR_HIP;                                                              \
         }                                                                                    \
     } while (0)

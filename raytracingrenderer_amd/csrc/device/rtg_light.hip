@@ -93,6 +93,27 @@ RTG_D bool connect_to_camera(const DevProj& c, v3 p, v3 n, v3 col, int& pixel, v
     return true;
 }
 
+// rtg_probe_connect: connect_to_camera on given points (out: 12 floats per point, zero where rejected)
+__global__ void k_probe_connect(DevProj cam, const float* pts, const float* nrm, const float* col, unsigned n,
+                                float* out) {
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float* o = out + (size_t)i * 12;
+    for (int k = 0; k < 12; ++k) o[k] = 0.0f;
+    int pixel;
+    v3 cc;
+    float4 so, sd;
+    if (!connect_to_camera(cam, mk(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]),
+                           mk(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]),
+                           mk(col[3 * i], col[3 * i + 1], col[3 * i + 2]), pixel, cc, so, sd))
+        return;
+    o[0] = __int_as_float(1);
+    o[1] = __int_as_float(pixel);
+    o[2] = cc.x; o[3] = cc.y; o[4] = cc.z;
+    o[5] = so.x; o[6] = so.y; o[7] = so.z; o[8] = so.w;
+    o[9] = sd.x; o[10] = sd.y; o[11] = sd.z;
+}
+
 // Block-level compaction of up to two queues (ballot + mbcnt in a wave, LDS prefix over the waves,
 // one atomic per queue per block). Every thread of the block must call it.
 RTG_D void compact2(bool wa, bool wb, unsigned id, unsigned* qa, unsigned* na, unsigned* qb, unsigned* nb) {
@@ -312,10 +333,12 @@ __global__ __launch_bounds__(RTG_TB) void k_light_collect(LightArgs a, PathBufs 
 
 // Film::splat in key order: one thread per pixel run of the sorted records.
 __global__ __launch_bounds__(RTG_TB) void k_light_splat(const unsigned long long* key, const unsigned* idx,
-                                                        const float4* col, unsigned n, float* film) {
+                                                        const float4* col, unsigned n, unsigned npix,
+                                                        float* film) {
     const unsigned r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     const unsigned long long pix = key[r] >> 40;
+    if (pix >= npix) return;  // connect_to_camera gives film pixels only; never write past the film
     if (r > 0 && (key[r - 1] >> 40) == pix) return;
     float* f = film + (size_t)pix * 3;
     float fr = f[0], fg = f[1], fb = f[2];
@@ -329,6 +352,16 @@ __global__ __launch_bounds__(RTG_TB) void k_light_splat(const unsigned long long
     f[0] = fr;
     f[1] = fg;
     f[2] = fb;
+}
+
+// Ray tally of a finished chunk or batch into stats[2..3] (extension, shadow), where rtg_get_stats reads
+// the ray counts from (k_tally's slots in rtg_render.hip): the host-side rtg_stats fields of the same
+// name are overwritten from them.
+__global__ void k_light_tally(unsigned long long* stats, unsigned long long ext, unsigned long long shadow) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        atomicAdd(&stats[2], ext);
+        atomicAdd(&stats[3], shadow);
+    }
 }
 
 __global__ void k_iota(unsigned* v, unsigned n) {
@@ -468,6 +501,13 @@ static DevProj make_proj(const rtg_handle* h) {
 
 static unsigned grid(size_t n) { return (unsigned)std::max<size_t>(1, (n + RTG_TB - 1) / RTG_TB); }
 
+static int tally_rays(rtg_handle* h, hipStream_t st, unsigned long long ext, unsigned long long shadow) {
+    if (!ext && !shadow) return RTG_OK;
+    hipLaunchKernelGGL(k_light_tally, dim3(1), dim3(64), 0, st, h->d_stats, ext, shadow);
+    LAUNCH_OK("k_light_tally");
+    return RTG_OK;
+}
+
 static int read_ctr(Counters* d, Counters& out, hipStream_t st) {
     HIPOK(hipMemcpyAsync(&out, d, sizeof(Counters), hipMemcpyDeviceToHost, st));
     HIPOK(hipStreamSynchronize(st));
@@ -493,7 +533,9 @@ static int trace_light_paths(rtg_handle* h, hipStream_t st, LightArgs& a, PathBu
     HIPOK(hipMemsetAsync(pb.ctr, 0, 2 * sizeof(Counters), st));
     hipLaunchKernelGGL(k_light_generate, dim3(grid(a.P)), dim3(RTG_TB), 0, st, h->sv, a, pb, pb.ctr, key, col, d_rec_n);
     LAUNCH_OK("k_light_generate");
-    h->stats.paths += a.P;
+    // counted into the handle's statistics only when the chunk completes: the caller retries a chunk
+    // whose records overflowed, and its first attempt's paths and rays must not be counted twice
+    unsigned long long n_ext = 0, n_shadow = 0;
     for (unsigned k = 0;; ++k) {
         const int c = k & 1;
         Counters cn;
@@ -504,8 +546,8 @@ static int trace_light_paths(rtg_handle* h, hipStream_t st, LightArgs& a, PathBu
         if ((size_t)rn + cn.n_shadow + cn.n_ext > cap) { g_err = "light tracing: record buffer overflow"; return RTG_ERR_HIP; }
         if (cn.n_ext == 0 && cn.n_shadow == 0) break;
         if (k >= 65535) { g_err = "light path longer than 65535 vertices"; return RTG_ERR_ARG; }
-        h->stats.extension_rays += cn.n_ext;
-        h->stats.shadow_rays += cn.n_shadow;
+        n_ext += cn.n_ext;
+        n_shadow += cn.n_shadow;
         // trace: extension rays of vertex k and camera connections of vertex k
         io.queue = pb.q[c];
         io.count = &pb.ctr[c].n_ext;
@@ -524,7 +566,8 @@ static int trace_light_paths(rtg_handle* h, hipStream_t st, LightArgs& a, PathBu
             LAUNCH_OK("k_light_shade");
         }
     }
-    return RTG_OK;
+    h->stats.paths += a.P;
+    return tally_rays(h, st, n_ext, n_shadow);
 }
 
 }  // namespace
@@ -561,8 +604,9 @@ int rtg_render_light(rtg_handle* h, uint32_t first, uint32_t n_frames, uint64_t 
             a.seed = seed;
             a.vpl = 0;
             a.cam = cam;
-            HIPOK(hipMemsetAsync(rn.p, 0, 16, st));
             for (;;) {  // grow the record buffers if a chunk overflows them (rare), then retry it
+                // every attempt of every chunk starts without records, as instant radiosity's loop does
+                HIPOK(hipMemsetAsync(rn.p, 0, 16, st));
                 rc = trace_light_paths(h, st, a, pb, key.get<unsigned long long>(), col.get<float4>(), rn.get<unsigned>(), cap);
                 if (rc == RTG_OK) break;
                 if (g_err != "light tracing: record buffer overflow") return rc;
@@ -570,7 +614,6 @@ int rtg_render_light(rtg_handle* h, uint32_t first, uint32_t n_frames, uint64_t 
                 (void)hipFree(key.p); (void)hipFree(col.p); (void)hipFree(key2.p); (void)hipFree(idx.p); (void)hipFree(idx2.p);
                 key.p = col.p = key2.p = idx.p = idx2.p = nullptr;
                 DALLOC(key, cap * 8); DALLOC(col, cap * 16); DALLOC(key2, cap * 8); DALLOC(idx, cap * 4); DALLOC(idx2, cap * 4);
-                HIPOK(hipMemsetAsync(rn.p, 0, 16, st));
             }
             unsigned n = 0;
             HIPOK(hipMemcpyAsync(&n, rn.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
@@ -590,7 +633,7 @@ int rtg_render_light(rtg_handle* h, uint32_t first, uint32_t n_frames, uint64_t 
             HIPOK(rocprim::radix_sort_pairs(tmp.p, need, key.get<unsigned long long>(), key2.get<unsigned long long>(),
                                             idx.get<unsigned>(), idx2.get<unsigned>(), n, 0, 64, st));
             hipLaunchKernelGGL(k_light_splat, dim3(grid(n)), dim3(RTG_TB), 0, st, key2.get<unsigned long long>(),
-                               idx2.get<unsigned>(), (const float4*)col.p, n, h->d_film);
+                               idx2.get<unsigned>(), (const float4*)col.p, n, (unsigned)npaths, h->d_film);
             LAUNCH_OK("k_light_splat");
         }
         h->spp += 1;  // render(): film->incrementSPP()
@@ -680,7 +723,7 @@ int rtg_render_instant_radiosity(rtg_handle* h, uint32_t first, uint32_t n_frame
         io.hits = pb.hits;
         io.fetch = &pb.ctr[0].f_ext;
         if ((rc = launch_trace(h, io, st))) return rc;
-        h->stats.extension_rays += npix;
+        if ((rc = tally_rays(h, st, npix, 0))) return rc;
         h->stats.paths += npix;
         hipLaunchKernelGGL(k_ir_first_hit, dim3(grid(npix)), dim3(RTG_TB), 0, st, h->sv, ca, pb, px.get<float4>(),
                            pn.get<float4>(), pf.get<float4>(), acc.get<float4>());
@@ -719,7 +762,7 @@ int rtg_render_instant_radiosity(rtg_handle* h, uint32_t first, uint32_t n_frame
                 unsigned ns = 0;
                 HIPOK(hipMemcpyAsync(&ns, qn.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
                 HIPOK(hipStreamSynchronize(st));
-                h->stats.shadow_rays += ns;
+                if ((rc = tally_rays(h, st, 0, ns))) return rc;
             }
         }
         hipLaunchKernelGGL(k_ir_splat, dim3(grid(npix)), dim3(RTG_TB), 0, st, (const unsigned*)h->d_pix, npix,
@@ -728,6 +771,27 @@ int rtg_render_instant_radiosity(rtg_handle* h, uint32_t first, uint32_t n_frame
         h->spp += 1;
     }
     HIPOK(hipStreamSynchronize(st));
+    return RTG_OK;
+}
+
+int rtg_probe_connect(rtg_handle* h, const float* points, const float* normals, const float* colours, uint32_t n,
+                      float* out) {
+    if (!h || !points || !normals || !colours || !out) { g_err = "rtg_probe_connect: null argument"; return RTG_ERR_ARG; }
+    if (n > 0x7fffffffu / 12u) { g_err = "rtg_probe_connect: too many points"; return RTG_ERR_ARG; }
+    if (n == 0) return RTG_OK;
+    HIPOK(hipSetDevice(h->device));
+    DevBuf d_pts, d_nrm, d_col, d_out;
+    const size_t in_bytes = (size_t)n * 3 * sizeof(float), out_bytes = (size_t)n * 12 * sizeof(float);
+    DALLOC(d_pts, in_bytes); DALLOC(d_nrm, in_bytes); DALLOC(d_col, in_bytes); DALLOC(d_out, out_bytes);
+    HIPOK(hipMemcpy(d_pts.p, points, in_bytes, hipMemcpyHostToDevice));
+    HIPOK(hipMemcpy(d_nrm.p, normals, in_bytes, hipMemcpyHostToDevice));
+    HIPOK(hipMemcpy(d_col.p, colours, in_bytes, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_probe_connect, dim3((n + 255) / 256), dim3(256), 0, nullptr, make_proj(h),
+                       (const float*)d_pts.p, (const float*)d_nrm.p, (const float*)d_col.p, (unsigned)n,
+                       d_out.get<float>());
+    HIPOK(hipGetLastError());
+    HIPOK(hipDeviceSynchronize());
+    HIPOK(hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost));
     return RTG_OK;
 }
 

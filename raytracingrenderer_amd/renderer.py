@@ -413,6 +413,19 @@ class RayTracer:
         _check(self._lib.rtg_render_instant_radiosity(self._h, first, n_frames, self.seed, n_vpl),
                self._lib.rtg_last_error)
 
+    def connect_probe(self, points, normals, colours):
+        """The light tracer's own connectToCamera on this tracer's camera, apart from its visibility
+        test (rtg_probe_connect, test surface), for n points, shading normals and colours ((n, 3) each).
+        Returns (n, 12) float32: accepted and pixel as int32 bits, the splatted colour, the shadow
+        ray's origin, maxT and direction; all zero where the connection is not accepted."""
+        p, nn, c = (np.ascontiguousarray(v, np.float32).reshape(-1, 3) for v in (points, normals, colours))
+        if not len(p) == len(nn) == len(c):
+            raise ValueError("connect_probe: points, normals and colours must have one length")
+        out = np.zeros((len(p), 12), np.float32)
+        _check(self._lib.rtg_probe_connect(self._h, N.ptr(p, C.c_float), N.ptr(nn, C.c_float), N.ptr(c, C.c_float),
+                                           len(p), N.ptr(out, C.c_float)), self._lib.rtg_last_error)
+        return out
+
     def synchronize(self):
         _check(self._lib.rtg_synchronize(self._h), self._lib.rtg_last_error)
 

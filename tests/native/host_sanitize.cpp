@@ -32,6 +32,11 @@ int or_render(or_scene* s, uint32_t first, uint32_t n_samples, uint64_t seed, co
               int threads, float* film, uint64_t* counts, int count);
 int or_set_camera_sampling(or_scene* s, int filter, float filter_radius, float lens_radius, float focal_distance);
 int or_set_env_table(or_scene* s, const uint32_t* entries, uint32_t W, uint32_t H);
+int or_render_light(or_scene* s, uint32_t first, uint32_t n_frames, uint64_t seed, float* film, uint64_t* counts);
+int or_render_ir(or_scene* s, uint32_t first, uint32_t n_frames, uint64_t seed, uint32_t n_vpl, float* film,
+                 uint64_t* counts);
+int or_connect_probe(or_scene* s, const float* pts, const float* nrm, const float* col, uint32_t n, float* out,
+                     float* info);
 }
 
 namespace {
@@ -197,6 +202,27 @@ void load_and_render(const std::string& dir, int width, int height, bool render,
                 if (or_set_camera_sampling(os, 2, 1.0f, 0.05f, 5.0f) != 0) g_fail = 1;
                 if (or_render(os, 1, 1, 1234, nullptr, 0, 2, film.data(), counts, 1) != 0) g_fail = 1;
                 if (or_set_env_table(os, nullptr, 0, 0) != 0) g_fail = 1;
+            }
+            // the light-path integrators with their counts, and the camera-connection probe on points in
+            // front of, at and behind the camera, far away, infinite and NaN
+            uint64_t lc[5] = {0, 0, 0, 0, 0};
+            if (or_render_light(os, 0, 1, 1234, film.data(), lc) != 0) g_fail = 1;
+            if (or_render_ir(os, 1, 1, 1234, 7, film.data(), lc) != 0) g_fail = 1;
+            if (or_render_light(os, 65535, 1, 1234, film.data(), nullptr) != 0) g_fail = 1;
+            {
+                const float* o = d->camera.origin;
+                const float inf = __builtin_inff(), nan = __builtin_nanf("");
+                const float pts[9][3] = {{o[0], o[1], o[2] - 1}, {o[0], o[1], o[2]}, {o[0], o[1], o[2] + 1},
+                                         {1e30f, -1e30f, 1e30f}, {inf, 0, 0}, {0, -inf, inf}, {nan, 0, 0},
+                                         {0, 0, nan}, {o[0] + 0.01f, o[1], o[2] - 3}};
+                float nrm[9][3], col[9][3], out[9 * 12], info[9 * 3];
+                for (int k = 0; k < 9; ++k)
+                    for (int c = 0; c < 3; ++c) {
+                        nrm[k][c] = c == 2 ? 1.0f : 0.0f;
+                        col[k][c] = k == 8 ? nan : 1.0f;
+                    }
+                if (or_connect_probe(os, &pts[0][0], &nrm[0][0], &col[0][0], 9, out, info) != 0) g_fail = 1;
+                if (or_connect_probe(os, &pts[0][0], &nrm[0][0], &col[0][0], 9, out, nullptr) != 0) g_fail = 1;
             }
             std::vector<uint8_t> rgb(film.size());
             rth_tonemap(info.width, info.height, film.data(), 1, 1.0f, rgb.data());

@@ -40,7 +40,8 @@ extern "C" {
  *    rtg_film_scatter takes the film's pixel count; rtg_stats.lane_idle_* appended
  *    (additive, still 6: the denoiser, rtg_denoise_* and rtg_group_denoise; camera sampling,
  *    rtg_*_camera_sampling and rtg_probe_camera_samples; environment light sampling,
- *    rtg_*_env_sampling, rtg_env_* and rtg_probe_env_samples; rtg_probe_connect) */
+ *    rtg_*_env_sampling, rtg_env_* and rtg_probe_env_samples; rtg_probe_connect; light selection,
+ *    rtg_*_light_sampling, rtg_light_* and rtg_probe_light_pick) */
 #define RTG_ABI_VERSION 6
 
 /* error codes */
@@ -272,8 +273,8 @@ int  rtg_probe_camera_samples(rtg_handle* h, const uint32_t* pixels, const uint3
  *                  !(st > 0) or !(pdf > 0): the sample contributes nothing (no shadow ray).
  *                  IEEE float32 in the order written, no contraction. The radiance stays the one
  *                  EnvironmentMap::evaluate(wi), and the shadow ray and Ld = f E g / (pmf pdf) stay as
- *                  they are (pmf = 1 / n_lights: no power-weighted light selection, no MIS with
- *                  BSDF-sampled environment hits).
+ *                  they are (pmf = 1 / n_lights, or the picked light's under rtg_set_light_sampling;
+ *                  no MIS with BSDF-sampled environment hits).
  *   DIRECT_MIS     computeDirectMIS keeps its structure (Renderer.h:474-557): pdf is the one variable
  *                  the light sample sets and the BSDF half reads. A visible environment sample returns
  *                  f E g / (pmf pdf) at once, unweighted, as in uniform mode. Otherwise (rejected, g = 0
@@ -315,6 +316,87 @@ int  rtg_probe_env_samples(rtg_handle* h, const uint32_t* r0, const float* d, ui
  * entry, and the n*4 words of the entries as uploaded. Weights summing to 0, n == 0 or
  * n > RTG_ENV_MAX_CELLS: RTG_ERR_ARG. */
 int  rtg_env_alias_build(const double* weights, uint32_t n, double* prob, uint32_t* alias, float* entries);
+
+/* ---- light selection for NEE (rtg_light_pick.hip). Scene::sampleLight picks the light
+ * of every NEE sample uniformly from the light list, one entry per emissive triangle plus possibly the
+ * environment: li = (int)(n_lights * u), pmf = 1 / n_lights (Scene.h:137-138). That is the default
+ * here, RTG_LIGHTS_UNIFORM, untouched: the same kernels, draws and bits. RTG_LIGHTS_POWER picks light i
+ * with a probability that grows with its emitted power, through an alias table over the light list
+ * (one 16-byte load per pick), mixed with the uniform pick by uniform_share (lambda in [0, 1]).
+ * Definition, for a light list of n entries:
+ *   weights        binary64, in light-list order. Area light i: w_i = (double)Lum(em) * (double)area,
+ *                  Lum = Colour::Lum in float32 on the device record's emission,
+ *                  ((0.2126f r) + (0.7152f g)) + (0.0722f b), a negative or non-finite value counting
+ *                  as 0, and area the float32 the device record holds (rtg_light_records: word 3).
+ *                  The environment light: w_env = (2.0 * pi * pi) * R * R * (S / N), S the §8c sum of
+ *                  the map's N = W * H cell weights (footprint maximum of Lum times sin theta, added in
+ *                  index order; computed whether or not RTG_ENV_LUMINANCE is on, and without building
+ *                  the environment's alias table), R = 0.5 * sqrt(dx*dx + dy*dy + dz*dz) half the
+ *                  diagonal of the reference root box, from its six float32 bounds widened to
+ *                  binary64 ((dx*dx + dy*dy) + dz*dz): the map's flux through the scene's bounding
+ *                  sphere over pi, on the footing of area * L for a one-sided diffuse emitter.
+ *   pmf            pmf_i = ((1 - lambda) * w_i) / sum + lambda / n in binary64, sum = the weights added
+ *                  in index order, lambda = (double)uniform_share.
+ *   table          n entries {prob (float), alias (uint32), pmf_self (float), pmf_alias (float)},
+ *                  pmf_* = (float)pmf. prob and alias are Vose's algorithm of §8c (the same builder,
+ *                  rtg_env_alias.h, in its fixed order, in binary64) run on p_k = pmf_k * n.
+ *                  An entry with pmf == 0 has prob == 0 exactly and is named by no alias. For every
+ *                  light i, prob_i / n + sum over {j: alias_j = i} of (1 - prob_j) / n is pmf_i (to
+ *                  binary64 rounding before prob is rounded to float).
+ *   draws          the pick takes two draws from the path's own PCG stream in place of the uniform
+ *                  pick's one, always both: r0, the raw 32-bit output of a PCG step, then d1, a float in
+ *                  [0, 1) as every other draw.
+ *   pick           k = (uint32)(((uint64)r0 * n) >> 32); e = table[k]; keep = d1 < e.prob;
+ *                  li = keep ? k : e.alias; pmf = keep ? e.pmf_self : e.pmf_alias.
+ *   after it       everything is what it is under the uniform pick with that pmf in 1 / n_lights' place:
+ *                  Triangle::sample's r1, r2 or the environment branch's two or four draws (according to
+ *                  rtg_set_env_sampling), Ld = f E g / (pmf * pdf), the shadow ray. IEEE float32 in the
+ *                  order written, no contraction. A power-mode film is another realisation of the same
+ *                  expectation, not the uniform film.
+ *   DIRECT_MIS     computeDirectMIS keeps its structure (Renderer.h:474-557), as in §8c: the value that
+ *                  travels to the BSDF half is pdf * pmf of the *sampled* light, and a BSDF-sampled
+ *                  emitter hit is weighted with it. That is the reference's reuse of the variable,
+ *                  inherited and not designed: the BSDF-hit emitter is not looked up for its own pmf.
+ *   fallbacks      n_lights == 1, a weight sum of 0 or not finite, or an environment light with R 0 or
+ *                  not finite: the mode is accepted, no table is built, and the kernels, draws and bits
+ *                  are the uniform pick's.
+ * uniform_share defaults to 0.125: it bounds 1 / pmf by 8 n, so a dim light next to a surface cannot
+ * produce unbounded weights. A robustness choice, not a measured optimum (DESIGN.md §8d has the error
+ * at 0, 0.125 and 0.5). uniform_share outside [0, 1] or NaN, or an unknown mode: RTG_ERR_ARG before any
+ * device call, and the previous setting stays. The weights, Vose and the upload run on the first
+ * RTG_LIGHTS_POWER setting of a handle and again when uniform_share changes; the table is kept until
+ * rtg_destroy; every rank of a group builds its own, the same bits. rtg_set_light_sampling first issues
+ * and waits for queued frames.
+ * The setting applies to rtg_render, rtg_render_async, rtg_render_adaptive and the group calls, under
+ * RTG_INTEGRATOR_PATH, _DIRECT and _DIRECT_MIS (kernels of their own, k_shade_pick; the default's are
+ * not touched), with either environment sampling mode. It does not apply to rtg_render_light and
+ * rtg_render_instant_radiosity (their light choice stays uniform), to the denoiser's guides or to
+ * RTG_INTEGRATOR_ALBEDO and _NORMALS, which sample no light. */
+#define RTG_LIGHTS_UNIFORM 0
+#define RTG_LIGHTS_POWER   1
+typedef struct rtg_light_sampling {
+    int32_t mode;          /* RTG_LIGHTS_* */
+    float uniform_share;   /* lambda in [0, 1] */
+} rtg_light_sampling;
+int  rtg_light_sampling_defaults(rtg_light_sampling* p);  /* {RTG_LIGHTS_UNIFORM, 0.125f} */
+int  rtg_set_light_sampling(rtg_handle* h, const rtg_light_sampling* p);
+int  rtg_get_light_sampling(rtg_handle* h, rtg_light_sampling* p);
+/* The n_lights weights the active table was built from (RTG_ERR_ARG when none is active). */
+int  rtg_light_weights(rtg_handle* h, double* weights);
+/* The active table: *n its entries (0 when no table is active: uniform mode or a fallback), entries
+ * (or NULL) n*4 32-bit words, build_ms (or NULL) the host time of its last build. */
+int  rtg_light_table(rtg_handle* h, uint32_t* n, float* entries, double* build_ms);
+/* The light records as uploaded, 20 floats per light: v0.xyz area | v1.xyz type bits (0 area, 1
+ * environment) | v2.xyz 1/area | geometric normal.xyz - | emission.rgb - . */
+int  rtg_light_records(rtg_handle* h, float* out /* n_lights * 20 */);
+/* The kernel's own pick on n scripted draws against the active table: li[n], pmf[n]. No active table:
+ * RTG_ERR_ARG. */
+int  rtg_probe_light_pick(rtg_handle* h, const uint32_t* r0, const float* d1, uint32_t n, int32_t* li, float* pmf);
+/* The host's builder alone (no device call): pmf, Vose's prob (binary64) and alias per entry, and the
+ * n*4 words of the entries as uploaded. n == 0, a negative or non-finite weight, weights summing to 0 or
+ * to a non-finite value, uniform_share outside [0, 1] or NaN: RTG_ERR_ARG. */
+int  rtg_light_pick_build(const double* weights, uint32_t n, double uniform_share, double* pmf, double* prob,
+                          uint32_t* alias, float* entries);
 
 /* Add samples [first_sample, first_sample+n_samples) of every pixel in the listed 32x32 tiles
  * (tile id = ty*tilesX + tx, RTBase TILE_SIZE=32; tile_ids=NULL = all tiles) to the film, in
@@ -406,6 +488,7 @@ rtg_handle* rtg_group_handle(rtg_group* g, int rank);  /* e.g. for rtg_get_stats
 int  rtg_group_set_options(rtg_group* g, int max_depth, int flags, uint32_t max_paths);
 int  rtg_group_set_camera_sampling(rtg_group* g, const rtg_camera_sampling* p);  /* every rank's handle */
 int  rtg_group_set_env_sampling(rtg_group* g, int mode);  /* rtg_set_env_sampling on every rank's handle */
+int  rtg_group_set_light_sampling(rtg_group* g, const rtg_light_sampling* p);  /* every rank's handle */
 int  rtg_group_render(rtg_group* g, uint32_t first_sample, uint32_t n_samples, uint64_t seed);
 int  rtg_group_reduce(rtg_group* g);  /* the films stay per device; the assembled film goes to a separate buffer */
 /* Queued forms (the frame loop of Main.cpp:74-118 on N devices). rtg_group_render_async is every

@@ -19,6 +19,7 @@ RTG_FILTER_NONE, RTG_FILTER_BOX, RTG_FILTER_TENT = 0, 1, 2
 RTG_FILTER_MAX_RADIUS = 4.0
 RTG_ENV_UNIFORM, RTG_ENV_LUMINANCE = 0, 1
 RTG_ENV_MAX_CELLS = 1 << 24
+RTG_LIGHTS_UNIFORM, RTG_LIGHTS_POWER = 0, 1
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
@@ -75,6 +76,10 @@ class rtg_denoise_params(C.Structure):
 class rtg_camera_sampling(C.Structure):
     _fields_ = [("filter", C.c_int32), ("filter_radius", C.c_float), ("lens_radius", C.c_float),
                 ("focal_distance", C.c_float)]
+
+
+class rtg_light_sampling(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("uniform_share", C.c_float)]
 
 
 class rth_load_options(C.Structure):
@@ -166,6 +171,17 @@ RTG_EXPORTS = [
     ("rtg_env_weights", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     ("rtg_probe_env_samples", C.c_int, [C.c_void_p, u32p, f32p, C.c_uint32, f32p]),
     ("rtg_env_alias_build", C.c_int, [C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), u32p, f32p]),
+    # light selection for NEE: the power-weighted alias table (rtg_light_pick.hip)
+    ("rtg_light_sampling_defaults", C.c_int, [C.POINTER(rtg_light_sampling)]),
+    ("rtg_set_light_sampling", C.c_int, [C.c_void_p, C.POINTER(rtg_light_sampling)]),
+    ("rtg_get_light_sampling", C.c_int, [C.c_void_p, C.POINTER(rtg_light_sampling)]),
+    ("rtg_group_set_light_sampling", C.c_int, [C.c_void_p, C.POINTER(rtg_light_sampling)]),
+    ("rtg_light_weights", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    ("rtg_light_table", C.c_int, [C.c_void_p, u32p, f32p, C.POINTER(C.c_double)]),
+    ("rtg_light_records", C.c_int, [C.c_void_p, f32p]),
+    ("rtg_probe_light_pick", C.c_int, [C.c_void_p, u32p, f32p, C.c_uint32, i32p, f32p]),
+    ("rtg_light_pick_build", C.c_int, [C.POINTER(C.c_double), C.c_uint32, C.c_double, C.POINTER(C.c_double),
+                                       C.POINTER(C.c_double), u32p, f32p]),
 ]
 
 RTH_EXPORTS = [

@@ -195,6 +195,7 @@ void rtg_destroy(rtg_handle* h) {
     if (h->entry) (void)hipEventDestroy(h->entry);
     denoise_release(h);
     (void)hipFree(h->d_env_table);
+    (void)hipFree(h->d_light_table);
     (void)hipFree(h->d_img);
     (void)hipFree(h->d_nodes); (void)hipFree(h->d_nodesq); (void)hipFree(h->d_leafbox); (void)hipFree(h->d_tris48); (void)hipFree(h->d_shade); (void)hipFree(h->d_mats);
     (void)hipFree(h->d_lights); (void)hipFree(h->d_texinfo); (void)hipFree(h->d_texels); (void)hipFree(h->d_film);

@@ -331,6 +331,22 @@ RTG_D bool env_sample_luminance(const EnvTable& e, uint32_t r0, float d1, float 
     return true;
 }
 
+// ------------------------------------------------------------------ light selection
+// rtg_set_light_sampling(.., RTG_LIGHTS_POWER) (include/rtg.h has the definition): the light an NEE
+// sample goes to, from an alias table over the light list: one 16-B load. entry = {prob, alias,
+// pmf_self, pmf_alias}. r0: a raw 32-bit draw; d1: a float in [0, 1). tab: the table (global memory,
+// or k_shade_pick's LDS copy). k_shade_pick's three pick sites and k_probe_light_pick share this body.
+struct LightPick {
+    const uint4* table;  // null: no table (the uniform pick)
+};
+RTG_D int light_pick(const uint4* tab, uint32_t n, uint32_t r0, float d1, float& pmf) {
+    const uint32_t k = (uint32_t)(((uint64_t)r0 * n) >> 32);
+    const uint4 t = tab[k];
+    const bool keep = d1 < __uint_as_float(t.x);
+    pmf = __uint_as_float(keep ? t.z : t.w);
+    return (int)(keep ? k : t.y);
+}
+
 // ------------------------------------------------------------------ camera sampling
 // rtg_set_camera_sampling (include/rtg.h): where sample `sample` of pixel `pixel` crosses the film
 // and the lens. The draws come from a PCG32 stream of their own, keyed like the path's but with the

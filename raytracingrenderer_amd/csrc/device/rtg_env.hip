@@ -49,18 +49,14 @@ EnvTable env_table_of(const rtg_handle* h) {
     return EnvTable{h->d_env_table, w * hh, w, hh};
 }
 
-// The handle's table, once: weights on the device, Vose on the host, entries uploaded. A black map
-// leaves no table (the sampler stays uniform).
-static int build_env_table(rtg_handle* h) {
-    const auto t0 = std::chrono::steady_clock::now();
+// The map's w * h cell weights (include/rtg.h): the footprint maxima from the texels on the device,
+// times the row's sin theta on the host. Waits for the handle's stream.
+int env_cell_weights(rtg_handle* h, std::vector<double>& wts) {
     const int w = h->sv.env_w, hh = h->sv.env_h;
     const uint32_t n = (uint32_t)w * (uint32_t)hh;
     float* d_max = nullptr;
-    uint4* d_tab = nullptr;
     std::vector<float> maxlum(n);
-    std::vector<uint32_t> entries;
-    std::vector<double> wts(n);
-    bool have = false;
+    wts.assign(n, 0.0);
     auto run = [&]() -> int {
         HIPOK(hipMalloc((void**)&d_max, (size_t)n * sizeof(float)));
         (void)hipGetLastError();  // drop any stale error left by other code on this thread (as render_impl does)
@@ -73,6 +69,24 @@ static int build_env_table(rtg_handle* h) {
             const double rs = std::sin(3.14159265358979323846 * ((double)cy + 0.5) / (double)hh);
             for (int cx = 0; cx < w; ++cx) wts[(size_t)cy * w + cx] = (double)maxlum[(size_t)cy * w + cx] * rs;
         }
+        return RTG_OK;
+    };
+    const int rc = run();
+    (void)hipFree(d_max);
+    return rc;
+}
+
+// The handle's table, once: weights on the device, Vose on the host, entries uploaded. A black map
+// leaves no table (the sampler stays uniform).
+static int build_env_table(rtg_handle* h) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint32_t n = (uint32_t)h->sv.env_w * (uint32_t)h->sv.env_h;
+    uint4* d_tab = nullptr;
+    std::vector<uint32_t> entries;
+    std::vector<double> wts;
+    bool have = false;
+    auto run = [&]() -> int {
+        if (int rc = env_cell_weights(h, wts)) return rc;
         rtg_env::Alias al;
         have = rtg_env::build_alias(wts.data(), n, al);
         if (!have) return RTG_OK;
@@ -83,7 +97,6 @@ static int build_env_table(rtg_handle* h) {
         return RTG_OK;
     };
     const int rc = run();
-    (void)hipFree(d_max);
     if (rc != RTG_OK) {
         (void)hipFree(d_tab);
         return rc;

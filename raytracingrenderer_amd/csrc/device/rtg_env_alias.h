@@ -16,27 +16,19 @@ struct Alias {
     std::vector<float> cellpdf;     // (float)(((w / sum) * n) / ((2.0 * pi) * pi)) per cell
 };
 
-// Vose's algorithm in double, in a fixed order: cells are scaled to p = (w / sum) * n and put on the
-// "small" (p < 1) or "large" stack in ascending index order; while both hold cells, the top small
-// cell s takes prob p[s] and the top large cell l as its alias, p[l] = (p[l] + p[s]) - 1.0, and l goes
-// back on the stack its new p belongs to. What remains keeps itself (prob 1). A zero weight gives
-// p = 0 exactly, hence prob 0. sum == 0 (nothing to sample): returns false.
-static inline bool build_alias(const double* w, uint32_t n, Alias& out) {
-    const double pi = 3.14159265358979323846;
+// Vose's algorithm in double, in a fixed order, on scaled probabilities p (p_k = probability_k * n;
+// consumed): cells are put on the "small" (p < 1) or "large" stack in ascending index order; while both
+// hold cells, the top small cell s takes prob p[s] and the top large cell l as its alias,
+// p[l] = (p[l] + p[s]) - 1.0, and l goes back on the stack its new p belongs to. What remains keeps
+// itself (prob 1). A zero weight (w: the values p was scaled from) gives p = 0 exactly, hence prob 0.
+// Fills out.prob and out.alias. (rtg_light_pick.hip runs it on p_k = pmf_k * n.)
+static inline void vose(std::vector<double>& p, const double* w, uint32_t n, Alias& out) {
     out.prob.assign(n, 1.0);
     out.alias.resize(n);
-    out.cellpdf.resize(n);
-    double sum = 0.0;
-    for (uint32_t i = 0; i < n; ++i) sum += w[i];
-    out.sum = sum;
-    if (!(sum > 0.0) || !(sum <= 1.7976931348623157e308)) return false;
-    std::vector<double> p(n);
     std::vector<uint32_t> small, large;
     small.reserve(n);
     large.reserve(n);
     for (uint32_t i = 0; i < n; ++i) {
-        p[i] = (w[i] / sum) * (double)n;
-        out.cellpdf[i] = (float)(p[i] / ((2.0 * pi) * pi));
         out.alias[i] = i;
         (p[i] < 1.0 ? small : large).push_back(i);
     }
@@ -52,6 +44,25 @@ static inline bool build_alias(const double* w, uint32_t n, Alias& out) {
     // left on the small stack by rounding alone (p within a few ulp of 1), or with a zero weight when
     // no large cell is left (not reachable with sum > 0): a zero-weight cell keeps prob 0 regardless
     for (uint32_t s : small) out.prob[s] = (w[s] > 0.0) ? 1.0 : 0.0;
+}
+
+// The environment table: cells are scaled to p = (w / sum) * n, then vose(). sum == 0 (nothing to
+// sample): returns false.
+static inline bool build_alias(const double* w, uint32_t n, Alias& out) {
+    const double pi = 3.14159265358979323846;
+    out.prob.assign(n, 1.0);
+    out.alias.resize(n);
+    out.cellpdf.resize(n);
+    double sum = 0.0;
+    for (uint32_t i = 0; i < n; ++i) sum += w[i];
+    out.sum = sum;
+    if (!(sum > 0.0) || !(sum <= 1.7976931348623157e308)) return false;
+    std::vector<double> p(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        p[i] = (w[i] / sum) * (double)n;
+        out.cellpdf[i] = (float)(p[i] / ((2.0 * pi) * pi));
+    }
+    vose(p, w, n, out);
     return true;
 }
 

@@ -381,6 +381,15 @@ struct rtg_handle {
     std::vector<uint32_t> env_entries;  // the table's host copy (rtg_env_table)
     std::vector<double> env_weights;    // the cell weights it was built from (rtg_env_weights)
     double env_build_ms = 0.0;          // host time of the build: weights kernel, copy, Vose, upload
+    // rtg_set_light_sampling (rtg_light_pick.hip): the alias table over the light list, built by the first
+    // RTG_LIGHTS_POWER setting, rebuilt when uniform_share changes, kept until rtg_destroy
+    rtg_light_sampling light_sampling{RTG_LIGHTS_UNIFORM, 0.125f};
+    bool light_built = false;           // the build has run for light_built_share (a fallback leaves no table)
+    float light_built_share = 0.0f;
+    uint4* d_light_table = nullptr;
+    std::vector<uint32_t> light_entries;  // the table's host copy (rtg_light_table)
+    std::vector<double> light_weights;    // the weights it was built from (rtg_light_weights)
+    double light_build_ms = 0.0;
 };
 #define RTG_CNT_PENDING 0xFFFFFFFFu
 
@@ -465,6 +474,17 @@ void denoise_release(rtg_handle* h);
 // rtg_env.hip: the table k_shade_env samples the environment light from under the handle's setting and
 // integrator, or one with a null pointer (uniform sampling: today's k_shade launches)
 EnvTable env_table_of(const rtg_handle* h);
+// rtg_env.hip: the environment map's w * h cell weights (the table's, and the environment light's weight
+// of rtg_set_light_sampling); waits for the handle's stream
+int env_cell_weights(rtg_handle* h, std::vector<double>& wts);
+// rtg_light_pick.hip: the table k_shade_pick picks the NEE light from under the handle's setting and
+// integrator, or one with a null pointer (the uniform pick: today's k_shade / k_shade_env launches)
+LightPick light_pick_of(const rtg_handle* h);
+// RTG_ERR_ARG (with "who: ..." as the message) for a setting outside include/rtg.h's ranges
+int light_sampling_check(const char* who, const rtg_light_sampling* p);
+// one k_shade_pick launch (ALT, TAB; ENV = env with a table) for bounce b
+int launch_shade_pick(bool alt, bool tab, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
+                      const PathBufs& p, int b, const EnvTable& env, const LightPick& pick);
 // rtg_shade.hip: one k_shade launch of `grid` blocks (ALT = alt, TAB = tab) for bounce b
 // (env with a table: k_shade_env, the ALT kernel with the environment light's alias-table sample)
 int launch_shade(bool alt, bool tab, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,

@@ -488,6 +488,26 @@ int rtg_group_set_env_sampling(rtg_group* g, int mode) {
     return RTG_OK;
 }
 
+int rtg_group_set_light_sampling(rtg_group* g, const rtg_light_sampling* p) {
+    if (!g) { g_err = "rtg_group_set_light_sampling: null group"; return RTG_ERR_ARG; }
+    // checked once for all ranks, so an argument error leaves every rank's setting as it was; every rank
+    // builds its own table, the same bits from the same records
+    if (int rc = light_sampling_check("rtg_group_set_light_sampling", p)) return rc;
+    for (rtg_handle* h : g->h) {
+        rtg_light_sampling prev{RTG_LIGHTS_UNIFORM, 0.125f};
+        (void)rtg_get_light_sampling(h, &prev);
+        const int rc = rtg_set_light_sampling(h, p);
+        if (rc) {
+            for (rtg_handle* u : g->h) {
+                if (u == h) break;
+                (void)rtg_set_light_sampling(u, &prev);
+            }
+            return rc;
+        }
+    }
+    return RTG_OK;
+}
+
 int rtg_group_render(rtg_group* g, uint32_t first_sample, uint32_t n_samples, uint64_t seed) {
     if (!g) return RTG_ERR_ARG;
     g->reduced = false;

@@ -619,7 +619,10 @@ static int issue_chunk(rtg_handle* h, ChunkSlot& sl, const ChunkArgs& a, int max
                 const bool tab = h->sv.n_mats <= RTG_LDS_MATS && h->sv.n_lights <= RTG_LDS_LIGHTS;
                 const bool alt = h->integrator != RTG_INTEGRATOR_PATH;
                 const EnvTable et = env_table_of(h);  // RTG_ENV_LUMINANCE with a table: k_shade_env
-                if ((rc = launch_shade(alt, tab, 8 * tiles, ss, h->sv, a, pb, b - 1, &et))) return rc;
+                const LightPick pk = light_pick_of(h);  // RTG_LIGHTS_POWER with a table: k_shade_pick
+                if (pk.table) rc = launch_shade_pick(alt, tab, 8 * tiles, ss, h->sv, a, pb, b - 1, et, pk);
+                else rc = launch_shade(alt, tab, 8 * tiles, ss, h->sv, a, pb, b - 1, &et);
+                if (rc) return rc;
                 timed_end(h, ss, kinds, 2);
             }
         }

@@ -25,6 +25,8 @@ template <bool ALT, bool TAB>
 __global__ __launch_bounds__(RTG_TB, RTG_SHADE_WAVES) void k_shade(SceneView s, ChunkArgs a, PathBufs p, int b) {
     constexpr bool ENV = false;  // EnvironmentMap::sample's uniform sphere; the table branch compiles away
     const EnvTable et{nullptr, 0u, 0u, 0u};
+    constexpr bool PICK = false;  // Scene::sampleLight's uniform pick (k_shade_pick: rtg_light_pick.hip)
+    const LightPick lpk{nullptr};
 #include "rtg_shade_body.h"
 }
 // k_shade with the environment light sampled through the alias table (RTG_ENV_LUMINANCE): kernels of
@@ -37,6 +39,8 @@ template <bool ALT, bool TAB>
 __global__ __launch_bounds__(RTG_TB, ALT ? RTG_SHADE_ENV_ALT_WAVES : RTG_SHADE_WAVES) void k_shade_env(
     SceneView s, ChunkArgs a, PathBufs p, int b, EnvTable et) {
     constexpr bool ENV = true;
+    constexpr bool PICK = false;
+    const LightPick lpk{nullptr};
 #include "rtg_shade_body.h"
 }
 

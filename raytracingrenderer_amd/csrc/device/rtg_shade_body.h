@@ -7,11 +7,17 @@
 // two) at the two EnvironmentMap::sample sites. k_shade sets ENV = false, and the compiler then emits
 // for its four instantiations the instructions it emitted before the branch existed (sharing the body
 // as an inlined function did not: DESIGN.md 8c).
+// PICK = true (k_shade_pick, rtg_light_pick.hip; the including kernel also sets the LightPick lpk): the
+// light of an NEE sample comes from the power-weighted alias table (rtg_set_light_sampling,
+// RTG_LIGHTS_POWER: two draws r0, d1 in place of the uniform pick's one) with the entry's pmf in
+// s.pmf's place, at the three sites that draw li or read s.pmf. k_shade and k_shade_env set PICK =
+// false and keep their instructions.
     __shared__ unsigned s_cnt[2][RTG_TB / 64];
     __shared__ unsigned s_base[2];
     __shared__ float4 s_sho[RTG_TB], s_shd[RTG_TB];  // NEE ray staged until its queue position is known
     __shared__ DevMat s_mat[TAB ? RTG_LDS_MATS : 1];
     __shared__ DevLight s_lt[TAB ? RTG_LDS_LIGHTS : 1];
+    __shared__ uint4 s_pk[(PICK && TAB) ? RTG_LDS_LIGHTS : 1];  // the light-pick table (one entry per light)
     const int lane = lane_id();
     const int wave = threadIdx.x >> 6;
     const bool lean0 = b == 0;  // bounce 0: path id = position, camera origin, thr 1, PCG seed, canHitLight
@@ -47,6 +53,8 @@
         if ((int)threadIdx.x < 5 * s.n_lights)
             __builtin_amdgcn_global_load_lds((gptr_t)(reinterpret_cast<const float4*>(s.lights) + threadIdx.x),
                                              (lptr_t)(reinterpret_cast<float4*>(s_lt) + w0), 16, 0, 0);
+        if (PICK && (int)threadIdx.x < s.n_lights)  // n_lights <= RTG_LDS_LIGHTS < 64: wave 0's lanes
+            __builtin_amdgcn_global_load_lds((gptr_t)(lpk.table + threadIdx.x), (lptr_t)(s_pk + w0), 16, 0, 0);
     }
     // one 256-path tile per block: a finished block frees its slot for the next tile
     {
@@ -97,6 +105,7 @@
             int stage = 0, mid = 0;
             v3 env_dir = d, x = o, sn = d, alb = d, l_p2 = o, l_em = d;
             float l_g = 0.0f, l_pdf = 0.0f;
+            float l_pp = 0.0f;  // PICK: the picked light's pmf * l_pdf (one value across the lookup, not two)
             if (ALT && a.mode == RTG_INTEGRATOR_DIRECT_MIS && b == 1) {
                 // computeDirectMIS, second half (Renderer.h:520-553): the BSDF-sampled ray's hit.
                 // thr = (bsdf value, bsdf pdf); scratch planes 2/3 = (x, light pdf * pmf) and
@@ -157,9 +166,17 @@
                     c = mk(0.0f, 0.0f, 0.0f);
                     if (!(M.kind == RTG_MAT_MIRROR || M.kind == RTG_MAT_GLASS)) {
                         const int nl = s.n_lights;
-                        const float pmf = s.pmf;  // 1.f / (float)nl
-                        int li = (int)((float)nl * pcg_next(st, inc));
-                        li = (nl - 1) < li ? (nl - 1) : li;
+                        float pmf;
+                        int li;
+                        if (PICK) {  // RTG_LIGHTS_POWER: r0, d1, always both
+                            const uint32_t r0 = pcg_step(st, inc);
+                            const float d1 = pcg_next(st, inc);
+                            li = light_pick(TAB ? s_pk : lpk.table, (uint32_t)nl, r0, d1, pmf);
+                        } else {
+                            pmf = s.pmf;  // 1.f / (float)nl
+                            li = (int)((float)nl * pcg_next(st, inc));
+                            li = (nl - 1) < li ? (nl - 1) : li;
+                        }
                         const DevLight L = TAB ? s_lt[li] : s.lights[li];
                         const v3 f = divs_pi(tex_sample(s, M, tu, tv));  // BSDF::evaluate
                         float pdf;
@@ -249,8 +266,16 @@
                     alb = tex_sample(s, M, tu, tv);
                     if (!spec) {
                         const int nl = s.n_lights;
-                        int li = (int)((float)nl * pcg_next(st, inc));
-                        li = (nl - 1) < li ? (nl - 1) : li;  // (std::min)(a, b)
+                        float pmf = 0.0f;
+                        int li;
+                        if (PICK) {  // RTG_LIGHTS_POWER: r0, d1, always both
+                            const uint32_t r0 = pcg_step(st, inc);
+                            const float d1 = pcg_next(st, inc);
+                            li = light_pick(TAB ? s_pk : lpk.table, (uint32_t)nl, r0, d1, pmf);
+                        } else {
+                            li = (int)((float)nl * pcg_next(st, inc));
+                            li = (nl - 1) < li ? (nl - 1) : li;  // (std::min)(a, b)
+                        }
                         const DevLight L = TAB ? s_lt[li] : s.lights[li];
                         if (__float_as_int(L.v1t.w) == 0) {  // AreaLight::sample -> Triangle::sample
                             const float r1 = pcg_next(st, inc);
@@ -287,6 +312,7 @@
                             env_need = l_g > 0;
                             env_light = true;
                         }
+                        if (PICK) l_pp = pmf * l_pdf;
                     }
                     stage = 1;
                 }
@@ -305,7 +331,7 @@
                 bool ld_pre = false;  // contrib takes the visible NEE value now
                 v3 cpre = ld;
                 if (!spec && l_g > 0) {
-                    const float pmf = s.pmf;  // 1.f / (float)nl
+                    const float pmf = s.pmf;  // 1.f / (float)nl (PICK: the picked light's, inside l_pp)
                     const v3 emitted = env_light ? E : l_em;
                     // Scene::visible(x, p2)
                     v3 sd = sub(l_p2, x);
@@ -313,7 +339,7 @@
                     sd = normalize(sd);
                     const v3 so = add(x, muls(sd, RTG_EPS));
                     const v3 f = divs_pi(alb);  // BSDF::evaluate
-                    ld = divs(muls(mul(f, emitted), l_g), pmf * l_pdf);
+                    ld = divs(muls(mul(f, emitted), l_g), PICK ? l_pp : pmf * l_pdf);
                     const v3 cvis = mul(thr, ld);
                     s_sho[threadIdx.x] = make_float4(so.x, so.y, so.z, maxt);
                     // Visible is the common case: contrib takes thr * Ld now and k_trace

@@ -27,6 +27,10 @@
 // Environment light sampling (rtg_set_env_sampling): -envSampling uniform|luminance (uniform: the
 // reference's EnvironmentMap::sample; luminance: NEE directions drawn in proportion to the map's
 // luminance through an alias table), for one device and for -gpus / -devices alike.
+// Light selection for NEE (rtg_set_light_sampling): -lightSampling uniform|power (uniform: the
+// reference's Scene::sampleLight; power: lights picked by emitted power through an alias table) and
+// -lightUniformShare x (the share of the uniform pick mixed in, default 0.125), for one device and for
+// -gpus / -devices alike.
 // Multi-GPU (one node): -gpus N renders on devices 0..N-1, -devices a,b,... on a list. Rank r
 // renders the 32x32 tiles with (tile_x + tile_y) % N == r, and the film is assembled on the first
 // device from every device's own tiles (packed, one RCCL send per device, scattered) before it is
@@ -105,6 +109,12 @@ int main(int argc, char** argv) {
     const std::string es = get("-envSampling", "uniform");
     if (es != "uniform" && es != "luminance") return die("-envSampling", "one of uniform, luminance");
     const int env_mode = es == "luminance" ? RTG_ENV_LUMINANCE : RTG_ENV_UNIFORM;
+    rtg_light_sampling lsm{};
+    rtg_light_sampling_defaults(&lsm);
+    const std::string lsn = get("-lightSampling", "uniform");
+    if (lsn != "uniform" && lsn != "power") return die("-lightSampling", "one of uniform, power");
+    lsm.mode = lsn == "power" ? RTG_LIGHTS_POWER : RTG_LIGHTS_UNIFORM;
+    lsm.uniform_share = std::stof(get("-lightUniformShare", "0.125"));
     rtg_handle* rt = nullptr;
     rtg_group* grp = nullptr;
     if (devices.empty()) {
@@ -112,12 +122,14 @@ int main(int argc, char** argv) {
         if (rtg_set_options(rt, max_depth, RTG_OPT_CULL, 0) != 0) return die("rtg_set_options", rtg_last_error());
         if (rtg_set_camera_sampling(rt, &cs) != 0) return die("rtg_set_camera_sampling", rtg_last_error());
         if (rtg_set_env_sampling(rt, env_mode) != 0) return die("rtg_set_env_sampling", rtg_last_error());
+        if (rtg_set_light_sampling(rt, &lsm) != 0) return die("rtg_set_light_sampling", rtg_last_error());
     } else {
         if (rtg_group_create(devices.data(), (int)devices.size(), rth_scene_desc(scene), &grp) != 0)
             return die("rtg_group_create", rtg_last_error());
         if (rtg_group_set_options(grp, max_depth, RTG_OPT_CULL, 0) != 0) return die("rtg_group_set_options", rtg_last_error());
         if (rtg_group_set_camera_sampling(grp, &cs) != 0) return die("rtg_group_set_camera_sampling", rtg_last_error());
         if (rtg_group_set_env_sampling(grp, env_mode) != 0) return die("rtg_group_set_env_sampling", rtg_last_error());
+        if (rtg_group_set_light_sampling(grp, &lsm) != 0) return die("rtg_group_set_light_sampling", rtg_last_error());
         std::printf("%d devices, own-tile film exchange by %s\n", (int)devices.size(),
                     rtg_group_uses_rccl(grp) ? "RCCL (ncclSend/ncclRecv)"
                     : devices.size() == 1    ? "none (one device)"

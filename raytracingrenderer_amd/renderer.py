@@ -225,6 +225,19 @@ def _env_mode(mode):
     return int(mode)
 
 
+LIGHT_SAMPLING = {"uniform": N.RTG_LIGHTS_UNIFORM, "power": N.RTG_LIGHTS_POWER}
+
+
+def _light_sampling(mode, uniform_share):
+    """The rtg_light_sampling of set_light_sampling's arguments (a name of LIGHT_SAMPLING or a value; an
+    unknown value or a share outside [0, 1] is the library's error)."""
+    if isinstance(mode, str):
+        if mode not in LIGHT_SAMPLING:
+            raise ValueError("unknown light sampling %r (one of %s)" % (mode, ", ".join(LIGHT_SAMPLING)))
+        mode = LIGHT_SAMPLING[mode]
+    return N.rtg_light_sampling(int(mode), float(uniform_share))
+
+
 class RayTracer:
     """RayTracer (Renderer.h:31-899) backed by librtg on one GPU."""
 
@@ -339,6 +352,63 @@ class RayTracer:
         _check(self._lib.rtg_probe_env_samples(self._h, N.ptr(r, C.c_uint32), N.ptr(dd, C.c_float), len(r),
                                                N.ptr(out, C.c_float)), self._lib.rtg_last_error)
         return out[:, :3].copy(), out[:, 3].copy()
+
+    def set_light_sampling(self, mode="uniform", uniform_share=0.125):
+        """Which light an NEE sample goes to (rtg_set_light_sampling). "uniform" (default):
+        Scene::sampleLight's pick, every entry of the light list (one per emissive triangle, plus the
+        environment) equally often, the reference's films bit for bit. "power": light i with probability
+        (1 - uniform_share) * w_i / sum(w) + uniform_share / n, w its luminance times area (the
+        environment: its map's flux through the scene's bounding sphere over pi), through an alias
+        table: the same expectation with less noise where a few lights carry most of the power; it
+        draws two numbers per pick instead of one, so its films are not the uniform mode's. One light,
+        or no power at all, keeps the uniform pick. Applies to render(), adaptiveRender() and the "path",
+        "direct" and "direct_mis" integrators; not to lightTracer(), instantRadiosity(), the denoiser's
+        guides, "albedo" or "normals"."""
+        p = _light_sampling(mode, uniform_share)
+        _check(self._lib.rtg_set_light_sampling(self._h, C.byref(p)), self._lib.rtg_last_error)
+
+    def light_sampling(self):
+        """The current setting: {"mode": "uniform" or "power", "uniform_share"}."""
+        p = N.rtg_light_sampling()
+        _check(self._lib.rtg_get_light_sampling(self._h, C.byref(p)), self._lib.rtg_last_error)
+        return {"mode": {v: k for k, v in LIGHT_SAMPLING.items()}.get(p.mode, p.mode), "uniform_share": p.uniform_share}
+
+    def light_table(self):
+        """The active light-pick table (rtg_light_table): a dict of "prob" (n,) float32, "alias" (n,)
+        uint32, "pmf_self" and "pmf_alias" (n,) float32, "entries" (n, 4) uint32 (the words as the kernel
+        loads them), "weights" (n,) float64 and "build_ms"; None when no table is active (uniform mode,
+        one light, no power)."""
+        n, ms = C.c_uint32(), C.c_double()
+        _check(self._lib.rtg_light_table(self._h, C.byref(n), None, C.byref(ms)), self._lib.rtg_last_error)
+        if n.value == 0:
+            return None
+        e = np.zeros((n.value, 4), np.float32)
+        _check(self._lib.rtg_light_table(self._h, C.byref(n), N.ptr(e, C.c_float), None), self._lib.rtg_last_error)
+        wt = np.zeros(n.value, np.float64)
+        _check(self._lib.rtg_light_weights(self._h, N.ptr(wt, C.c_double)), self._lib.rtg_last_error)
+        u = e.view(np.uint32)
+        return {"prob": e[:, 0].copy(), "alias": u[:, 1].copy(), "pmf_self": e[:, 2].copy(),
+                "pmf_alias": e[:, 3].copy(), "entries": u.copy(), "weights": wt, "build_ms": ms.value}
+
+    def light_records(self):
+        """The light records as uploaded (rtg_light_records): (n_lights, 20) float32 = v0.xyz area |
+        v1.xyz type bits (0 area, 1 environment) | v2.xyz 1/area | geometric normal.xyz - | emission.rgb -."""
+        out = np.zeros((len(self.scene.lights), 20), np.float32)
+        _check(self._lib.rtg_light_records(self._h, N.ptr(out, C.c_float)), self._lib.rtg_last_error)
+        return out
+
+    def light_picks(self, r0, d1):
+        """The shading kernel's own light pick (rtg_probe_light_pick) for scripted draws r0 (n,) uint32
+        and d1 (n,) float32 against the active table: (li (n,) int32, pmf (n,) float32)."""
+        r = np.ascontiguousarray(r0, np.uint32).reshape(-1)
+        d = np.ascontiguousarray(d1, np.float32).reshape(-1)
+        if len(r) != len(d):
+            raise ValueError("light_picks: r0 and d1 must have one length")
+        li = np.zeros(len(r), np.int32)
+        pmf = np.zeros(len(r), np.float32)
+        _check(self._lib.rtg_probe_light_pick(self._h, N.ptr(r, C.c_uint32), N.ptr(d, C.c_float), len(r),
+                                              N.ptr(li, C.c_int32), N.ptr(pmf, C.c_float)), self._lib.rtg_last_error)
+        return li, pmf
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -555,6 +625,11 @@ class RayTracerGroup:
     def set_env_sampling(self, mode="uniform"):
         """RayTracer.set_env_sampling on every rank (rtg_group_set_env_sampling)."""
         _check(self._lib.rtg_group_set_env_sampling(self._g, _env_mode(mode)), self._lib.rtg_last_error)
+
+    def set_light_sampling(self, mode="uniform", uniform_share=0.125):
+        """RayTracer.set_light_sampling on every rank (rtg_group_set_light_sampling)."""
+        p = _light_sampling(mode, uniform_share)
+        _check(self._lib.rtg_group_set_light_sampling(self._g, C.byref(p)), self._lib.rtg_last_error)
 
     def setup_ms(self):
         """(host build of the device records, parallel uploads) of rtg_group_create, in ms."""

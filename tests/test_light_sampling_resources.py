@@ -1,0 +1,91 @@
+"""Register budget around the light-selection kernels (compiled here for gfx950, no GPU needed):
+RTG_LIGHTS_POWER lives in kernels of its own (k_shade_pick, rtg_light_pick.hip), so the default's
+k_shade and k_shade_env instantiations must be no larger than on the commit before it, and the new
+kernels must hold their state in registers (DESIGN.md §8d has the table)."""
+import os
+import re
+import subprocess
+import tempfile
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DEVICE = os.path.join(ROOT, "raytracingrenderer_amd", "csrc", "device")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+# The figures of the commit before k_shade_pick, same flags, compiled once: (VGPRs, SGPRs, LDS bytes,
+# spilled VGPRs, spilled SGPRs, scratch bytes). k_shade<true, *> spilled then as it does now.
+BEFORE = {
+    "_Z7k_shadeILb0ELb1E": (64, 88, 16168, 0, 0, 0),
+    "_Z7k_shadeILb0ELb0E": (62, 87, 8232, 0, 0, 0),
+    "_Z7k_shadeILb1ELb1E": (72, 94, 16168, 60, 6, 128),
+    "_Z7k_shadeILb1ELb0E": (72, 94, 8232, 46, 20, 128),
+    "_Z11k_shade_envILb0ELb1E": (64, 92, 16168, 0, 0, 0),
+    "_Z11k_shade_envILb0ELb0E": (64, 91, 8232, 0, 0, 0),
+    "_Z11k_shade_envILb1ELb1E": (108, 106, 16168, 0, 0, 0),
+    "_Z11k_shade_envILb1ELb0E": (108, 106, 8232, 0, 4, 0),
+}
+KEYS = ("vgpr_count", "sgpr_count", "group_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count",
+        "private_segment_fixed_size")
+
+
+@pytest.fixture(scope="module")
+def kernels():
+    if not os.path.exists(HIPCC):
+        pytest.skip("hipcc not available")
+    from raytracingrenderer_amd.build import DEVICE_CXXFLAGS, DEVICE_FLAGS, DEVICE_SRC
+    assert "device/rtg_light_pick.hip" in DEVICE_SRC
+    assert DEVICE_FLAGS["device/rtg_light_pick.hip"] == DEVICE_FLAGS["device/rtg_shade.hip"]
+    res = {}
+    procs = []
+    with tempfile.TemporaryDirectory() as d:
+        for rel in ("device/rtg_shade.hip", "device/rtg_light_pick.hip"):
+            out = os.path.join(d, os.path.basename(rel) + ".s")
+            flags = [f for f in DEVICE_CXXFLAGS if f != "-fPIC"]
+            procs.append((out, subprocess.Popen([HIPCC, "--offload-arch=gfx950"] + flags + DEVICE_FLAGS.get(rel, []) +
+                                                ["--cuda-device-only", "-S", "-o", out,
+                                                 os.path.join(DEVICE, os.path.basename(rel))],
+                                                stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
+        for out, pr in procs:
+            log = pr.communicate()[0]
+            assert pr.returncode == 0, log.decode(errors="replace")
+            s = open(out).read()
+            md = s[s.index("amdhsa.kernels"):]
+            for blk in md.split("  - .agpr_count")[1:]:
+                name = re.search(r"\.name:\s+(\S+)", blk).group(1)
+                res[name] = {k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1)) for k in KEYS}
+    return res
+
+
+def _find(kernels, prefix):
+    names = [k for k in kernels if k.startswith(prefix)]
+    assert len(names) == 1, (prefix, names)
+    return kernels[names[0]]
+
+
+def test_new_kernels_hold_their_state_in_registers(kernels):
+    """The eight k_shade_pick instantiations and the probe: no spilled VGPR, no scratch. The pathTrace
+    instantiations k_shade_pick<false, *, *> keep k_shade<false, *>'s 7 waves per SIMD (<= 72 VGPRs, <= 96
+    SGPRs); the others take k_shade_env<true, *>'s 4-wave bound (<= 128 VGPRs). The LDS copy of the table
+    costs the TAB instantiations 768 bytes."""
+    pick = [k for k in kernels if "k_shade_pick" in k]
+    probe = [k for k in kernels if "k_probe_light_pick" in k]
+    assert len(pick) == 8 and len(probe) == 1, (pick, probe)
+    for name in pick + probe:
+        k = kernels[name]
+        assert k["vgpr_spill_count"] == 0 and k["private_segment_fixed_size"] == 0, (name, k)
+    for tab in ("Lb0E", "Lb1E"):
+        for env in ("Lb0E", "Lb1E"):
+            k = _find(kernels, "_Z12k_shade_pickILb0E" + tab + env)
+            assert k["vgpr_count"] <= 72 and k["sgpr_count"] <= 96 and k["sgpr_spill_count"] == 0, k
+            assert k["group_segment_fixed_size"] == (16168 + 768 if tab == "Lb1E" else 8232), k
+            k = _find(kernels, "_Z12k_shade_pickILb1E" + tab + env)
+            assert k["vgpr_count"] <= 128, k
+            assert k["group_segment_fixed_size"] == (16168 + 768 if tab == "Lb1E" else 8232), k
+
+
+@pytest.mark.parametrize("name", sorted(BEFORE))
+def test_existing_shading_kernels_are_no_larger_than_before(kernels, name):
+    k = _find(kernels, name + "Ev")
+    for key, before in zip(KEYS, BEFORE[name]):
+        assert k[key] <= before, (key, k)

@@ -41,7 +41,8 @@ extern "C" {
  *    (additive, still 6: the denoiser, rtg_denoise_* and rtg_group_denoise; camera sampling,
  *    rtg_*_camera_sampling and rtg_probe_camera_samples; environment light sampling,
  *    rtg_*_env_sampling, rtg_env_* and rtg_probe_env_samples; rtg_probe_connect; light selection,
- *    rtg_*_light_sampling, rtg_light_* and rtg_probe_light_pick) */
+ *    rtg_*_light_sampling, rtg_light_* and rtg_probe_light_pick; the material model,
+ *    rtg_*_material_model, rtg_*_material_params and rtg_probe_material) */
 #define RTG_ABI_VERSION 6
 
 /* error codes */
@@ -398,6 +399,115 @@ int  rtg_probe_light_pick(rtg_handle* h, const uint32_t* r0, const float* d1, ui
 int  rtg_light_pick_build(const double* weights, uint32_t n, double uniform_share, double* pmf, double* prob,
                           uint32_t* alias, float* entries);
 
+/* ---- material model (rtg_shade_phys.hip, rtg_phys.h). RTBase's ConductorBSDF, PlasticBSDF
+ * and OrenNayarBSDF are stubs that shade as a cosine-sampled Lambertian (RTG_MAT_LAMBERT), and
+ * ShadingHelper::Dggx / lambdaGGX / Gggx return 1. That is the default here, RTG_MATERIALS_REFERENCE,
+ * untouched: the same kernels, draws and bits. Under RTG_MATERIALS_PHYSICAL a material whose parameter
+ * record (rtg_set_material_params, one per rtg_scene_desc.materials entry, in that order) carries the tag
+ * RTG_MODEL_CONDUCTOR, _PLASTIC or _ORENNAYAR shades with the model below; a record tagged
+ * RTG_MODEL_REFERENCE (diffuse, mirror, glass, and the rough dielectric, which stays the Lambert stub)
+ * shades as it does by default. Definition, in the local frame of the shading normal (z; the frame is
+ * Frame::fromVector's), wo = the direction back along the ray after the two-sided flip, IEEE float32 in
+ * the order written, no contraction; pi = (float)M_PI; dot(a, b) = (ax bx + ay by) + az bz:
+ *   parameters     alpha = 1.62142f * sqrtf(roughness), formed by the host as the reference's constructors
+ *                  form it; sigma = the Oren-Nayar width (scene.json "alpha"); eta, k the conductor's
+ *                  complex index per channel; int_ior, ext_ior the plastic coat's.
+ *   D(h)           a2 = alpha alpha; t = ((h.z h.z) (a2 - 1)) + 1; D = a2 / ((pi t) t)
+ *   Lambda(w)      t2 = ((w.x w.x) + (w.y w.y)) / (w.z w.z); Lambda = (sqrtf(1 + (a2 t2)) - 1) 0.5
+ *   G1(w), G       G1 = 1 / (1 + Lambda(w)); G(wi, wo) = G1(wi) G1(wo)
+ *   half vector    hs = wo + wi; l2 = dot(hs, hs); inv = 1 / sqrtf(l2); h = hs inv;
+ *                  ch = clamp01(0.5 (l2 inv)), the cosine wo.h = wi.h = |wo + wi| / 2 in a form that has
+ *                  the same bits with wo and wi swapped (clamp01(x) = max(0, min(x, 1))). !(l2 > 0), i.e.
+ *                  wo + wi = 0: the GGX lobe contributes 0 to evaluate and to PDF.
+ *   F_c(c)         ShadingHelper::fresnelCondutor (Materials.h:78-91) per channel: cos2 = c c; sin2 = 1 -
+ *                  cos2; n2k2 = (eta eta) + (k k); e = (eta 2) c; Fpa2 = (((n2k2 cos2) - e) + sin2) /
+ *                  (((n2k2 cos2) + e) + sin2); Fpe2 = ((n2k2 - e) + cos2) / ((n2k2 + e) + cos2);
+ *                  F = (Fpa2 + Fpe2) 0.5. A denominator that is not > 0 (eta = k = 0) makes its half 1.
+ *   F_d(c)         fresnelDielectric (Materials.h:55-77) at clamp01(c), entering the coat from outside as
+ *                  GlassBSDF calls it: iorInt = ext_ior, iorExt = int_ior (its clamp makes a NaN 1).
+ *   conductor      evaluate = (albedo F_c(ch)) ((D(h) G(wi, wo)) / ((4 wo.z) wi.z));
+ *                  PDF = (G1(wo) D(h)) / (4 wo.z); sample: visible normals (Heitz 2018), draws u1, u2:
+ *                  vh = normalize(alpha wo.x, alpha wo.y, wo.z); lensq = (vh.x vh.x) + (vh.y vh.y);
+ *                  t1 = lensq > 0 ? (-vh.y il, vh.x il, 0), il = 1 / sqrtf(lensq) : (1, 0, 0);
+ *                  t2 = cross(vh, t1); r = sqrtf(u1); (sn, cs) = sincosf(6.2831855f u2) of
+ *                  include/rtg_math.h; p1 = r cs; sh = 0.5 (1 + vh.z);
+ *                  p2 = ((1 - sh) sqrtf(max(0, 1 - (p1 p1)))) + (sh (r sn));
+ *                  p3 = sqrtf(max(0, (1 - (p1 p1)) - (p2 p2))); nh = ((t1 p1) + (t2 p2)) + (vh p3);
+ *                  ne = normalize(alpha nh.x, alpha nh.y, max(0, nh.z)); wi = (ne (2 dot(wo, ne))) - wo.
+ *   plastic        evaluate = fd + sp on every channel, fd = (albedo / pi) ((1 - F_d(wo.z)) (1 - F_d(wi.z))),
+ *                  sp = F_d(ch) ((D G) / ((4 wo.z) wi.z)): an untinted dielectric GGX coat over the
+ *                  diffuse base. Three draws, always all three: u0 chooses the lobe, the coat when
+ *                  u0 < ps, ps = 0.25 + (0.5 F_d(wo.z)), which lies in [0.25, 0.75], so both lobes are
+ *                  sampled wherever they are not zero; the coat takes (u1, u2) as the conductor does, the
+ *                  base cosineSampleHemisphere(u2, u1) (the first of the two -> r2, as the Lambert family).
+ *                  PDF = (ps pv) + ((1 - ps) (wi.z / M_PI)), pv the conductor's PDF, wi.z / M_PI in
+ *                  binary64 rounded to float as cosineHemispherePDF.
+ *   Oren-Nayar     s2 = sigma sigma; A = 1 - (s2 / (2 (s2 + 0.33))); B = (0.45 s2) / (s2 + 0.09);
+ *                  evaluate = (albedo / pi) (A + ((B max(0, (wi.x wo.x) + (wi.y wo.y))) / max(wi.z, wo.z))):
+ *                  the qualitative model with its sin alpha tan beta cos(dphi) reduced to products.
+ *                  Sampling and PDF: cosineSampleHemisphere with the Lambert family's two draws in their
+ *                  order, PDF = wi.z / M_PI.
+ *   sample         returns colour = evaluate(wo, wi) and pdf = PDF(wo, wi), computed by those two functions
+ *                  from the sampled wi.
+ *   delta lobes    a GGX lobe with alpha < RTG_ALPHA_DELTA is a delta lobe (coffee's plastics have
+ *                  roughness 0). The path tracer counts an emitter hit only after a camera or specular
+ *                  bounce and has no MIS, so a lobe that narrow lit by NEE alone would be all fireflies.
+ *                  A delta lobe is left out of evaluate, PDF and NEE; a ray sampled from it reflects about
+ *                  the normal, wi = (-wo.x, -wo.y, wo.z), carries canHitLight = 1 and skips the cosine
+ *                  factor, as MirrorBSDF does. Conductor: colour = albedo F_c(clamp01(wo.z)), pdf = 1, no
+ *                  draws, no NEE at the vertex. Plastic: decided per sample: the coat is chosen as above
+ *                  (u0 < ps), colour = F_d(wo.z) on every channel, pdf = ps; the base keeps its NEE and
+ *                  its samples (PDF = (1 - ps) (wi.z / M_PI)). 0.01 is roughness below 3.8e-5: a
+ *                  robustness choice, not a measured optimum.
+ *   guards         evaluate and PDF are 0 unless wo.z > 0 and wi.z > 0. sample with !(wo.z > 0), a sampled
+ *                  wi with !(wi.z > 0), or a PDF that is not in (0, FLT_MAX]: pdf = 0 and the path ends at
+ *                  this vertex (its NEE term stays), where the reference model would carry a zero
+ *                  throughput on. wo + wi = 0: see the half vector.
+ *   in the path    NEE: Ld = f E g / (pmf pdf) with f = evaluate(wo, sd), sd the shadow ray's direction
+ *                  normalize(p2 - x), in albedo / pi's place; everything else of computeDirect, and the
+ *                  light and environment sampling modes, as they are. Bounce: after Russian roulette, thr =
+ *                  ((thr colour) |dot(wi, sN)|) / pdf, or (thr colour) / pdf for a delta sample.
+ * The setting applies to rtg_render, rtg_render_async, rtg_render_adaptive and the group calls under
+ * RTG_INTEGRATOR_PATH and _DIRECT (kernels of their own, k_shade_phys; the default's are not touched), with
+ * either environment and light sampling mode, and only when the scene has a conductor, plastic or
+ * Oren-Nayar record: a scene without one keeps today's kernels and bits under both settings. It does not
+ * apply to RTG_INTEGRATOR_DIRECT_MIS, _ALBEDO and _NORMALS, to rtg_render_light and
+ * rtg_render_instant_radiosity, or to the denoiser's guides: they keep the reference model. Not modelled:
+ * rough dielectric transmission, LayeredBSDF, MIS between NEE and BSDF-sampled emitter hits.
+ * rtg_set_material_params copies n records (n must equal rtg_scene_desc.n_materials);
+ * rtg_material_params_check is its argument check alone (no handle, no device call): a null pointer, a
+ * wrong n, an unknown tag, or an alpha, sigma, eta, k, int_ior or ext_ior that is negative or not finite
+ * is RTG_ERR_ARG. rtg_set_material_model(PHYSICAL) before any parameters were set, or an unknown mode:
+ * RTG_ERR_ARG. Argument errors are reported before any device call and leave the previous setting and
+ * the film as they were. Both setters first issue and wait for queued frames. The device table (unique
+ * records, and one index per triangle, fetched by the hit's triangle id beside its shading record) is
+ * built when the mode is first switched on, rebuilt when the parameters change, and kept until
+ * rtg_destroy; the default upload is not changed by it. */
+#define RTG_MATERIALS_REFERENCE 0
+#define RTG_MATERIALS_PHYSICAL  1
+#define RTG_MODEL_REFERENCE 0   /* shade by rtg_material.kind, as the default does */
+#define RTG_MODEL_CONDUCTOR 1
+#define RTG_MODEL_PLASTIC   2
+#define RTG_MODEL_ORENNAYAR 3
+#define RTG_ALPHA_DELTA 0.01f
+typedef struct rtg_material_params {
+    int32_t model;                 /* RTG_MODEL_* */
+    float alpha;                   /* GGX width, 1.62142f * sqrtf(roughness) (conductor, plastic) */
+    float sigma;                   /* Oren-Nayar width */
+    float eta[3], k[3];            /* conductor */
+    float int_ior, ext_ior;        /* plastic */
+} rtg_material_params;
+int  rtg_material_params_check(const rtg_material_params* params, uint32_t n, uint32_t n_materials);
+int  rtg_set_material_params(rtg_handle* h, const rtg_material_params* params, uint32_t n);
+int  rtg_set_material_model(rtg_handle* h, int mode);
+int  rtg_get_material_model(rtg_handle* h, int* mode);
+/* The kernels' own sample / evaluate / PDF on n scripted cases, on the current device (no handle).
+ * cases: n*28 floats (model, alpha, sigma, int_ior, ext_ior, eta[3], k[3], albedo.rgb, sNormal.xyz, wo.xyz,
+ * draw[3], query wi.xyz, pad[2]; wo and the query in world space, taken into Frame::fromVector(sNormal));
+ * out: n*16 floats (wi.xyz world, colour.rgb, pdf, draws consumed, delta flag, evaluate(query).rgb,
+ * PDF(query), pad[3]). A model other than conductor, plastic or Oren-Nayar: RTG_ERR_ARG. */
+int  rtg_probe_material(const float* cases, uint32_t n, float* out);
+
 /* Add samples [first_sample, first_sample+n_samples) of every pixel in the listed 32x32 tiles
  * (tile id = ty*tilesX + tx, RTBase TILE_SIZE=32; tile_ids=NULL = all tiles) to the film, in
  * sample order per pixel. Equivalent to n_samples calls of RayTracer::render() with the
@@ -489,6 +599,8 @@ int  rtg_group_set_options(rtg_group* g, int max_depth, int flags, uint32_t max_
 int  rtg_group_set_camera_sampling(rtg_group* g, const rtg_camera_sampling* p);  /* every rank's handle */
 int  rtg_group_set_env_sampling(rtg_group* g, int mode);  /* rtg_set_env_sampling on every rank's handle */
 int  rtg_group_set_light_sampling(rtg_group* g, const rtg_light_sampling* p);  /* every rank's handle */
+int  rtg_group_set_material_params(rtg_group* g, const rtg_material_params* params, uint32_t n);  /* every rank's */
+int  rtg_group_set_material_model(rtg_group* g, int mode);  /* rtg_set_material_model on every rank's handle */
 int  rtg_group_render(rtg_group* g, uint32_t first_sample, uint32_t n_samples, uint64_t seed);
 int  rtg_group_reduce(rtg_group* g);  /* the films stay per device; the assembled film goes to a separate buffer */
 /* Queued forms (the frame loop of Main.cpp:74-118 on N devices). rtg_group_render_async is every

@@ -50,6 +50,13 @@ const rtg_scene_desc* rth_scene_desc(const rth_scene* s);
 int  rth_scene_get_info(const rth_scene* s, rth_scene_info* out);
 /* Index (pre-build load order) of each post-build triangle: the BVH permutation. */
 int  rth_scene_permutation(const rth_scene* s, uint32_t* out /* n_tris */);
+/* What SceneLoader.h:117-171 hands the BSDF constructors, one record per rtg_scene_desc.materials entry
+ * in that order (include/rtg.h: rtg_set_material_params): conductor eta, k and alpha = 1.62142f *
+ * sqrtf(roughness); plastic intIOR, extIOR and alpha; orennayar sigma, read from the key "alpha"; with
+ * the loader's defaults (roughness 1, intIOR 1.33, extIOR 1, alpha 1, eta and k 0). The rough dielectric
+ * keeps intIOR, extIOR and alpha under the tag RTG_MODEL_REFERENCE (no model uses them); every other bsdf:
+ * RTG_MODEL_REFERENCE, all parameters 0. The pointer lives as long as the scene. */
+const rtg_material_params* rth_scene_material_params(const rth_scene* s, uint32_t* n /* or NULL */);
 
 /* Film::save: divide the accumulated sum by spp and write RLE RGBE (.hdr). */
 int  rth_save_hdr(const char* path, int32_t width, int32_t height, const float* rgb_sum, uint32_t spp);

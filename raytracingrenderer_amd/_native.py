@@ -20,6 +20,9 @@ RTG_FILTER_MAX_RADIUS = 4.0
 RTG_ENV_UNIFORM, RTG_ENV_LUMINANCE = 0, 1
 RTG_ENV_MAX_CELLS = 1 << 24
 RTG_LIGHTS_UNIFORM, RTG_LIGHTS_POWER = 0, 1
+RTG_MATERIALS_REFERENCE, RTG_MATERIALS_PHYSICAL = 0, 1
+RTG_MODEL_REFERENCE, RTG_MODEL_CONDUCTOR, RTG_MODEL_PLASTIC, RTG_MODEL_ORENNAYAR = 0, 1, 2, 3
+RTG_ALPHA_DELTA = 0.01
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
@@ -80,6 +83,11 @@ class rtg_camera_sampling(C.Structure):
 
 class rtg_light_sampling(C.Structure):
     _fields_ = [("mode", C.c_int32), ("uniform_share", C.c_float)]
+
+
+class rtg_material_params(C.Structure):
+    _fields_ = [("model", C.c_int32), ("alpha", C.c_float), ("sigma", C.c_float), ("eta", C.c_float * 3),
+                ("k", C.c_float * 3), ("int_ior", C.c_float), ("ext_ior", C.c_float)]
 
 
 class rth_load_options(C.Structure):
@@ -182,6 +190,14 @@ RTG_EXPORTS = [
     ("rtg_probe_light_pick", C.c_int, [C.c_void_p, u32p, f32p, C.c_uint32, i32p, f32p]),
     ("rtg_light_pick_build", C.c_int, [C.POINTER(C.c_double), C.c_uint32, C.c_double, C.POINTER(C.c_double),
                                        C.POINTER(C.c_double), u32p, f32p]),
+    # the material model: physical conductor, plastic and Oren-Nayar (rtg_shade_phys.hip)
+    ("rtg_material_params_check", C.c_int, [C.POINTER(rtg_material_params), C.c_uint32, C.c_uint32]),
+    ("rtg_set_material_params", C.c_int, [C.c_void_p, C.POINTER(rtg_material_params), C.c_uint32]),
+    ("rtg_set_material_model", C.c_int, [C.c_void_p, C.c_int]),
+    ("rtg_get_material_model", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    ("rtg_group_set_material_params", C.c_int, [C.c_void_p, C.POINTER(rtg_material_params), C.c_uint32]),
+    ("rtg_group_set_material_model", C.c_int, [C.c_void_p, C.c_int]),
+    ("rtg_probe_material", C.c_int, [f32p, C.c_uint32, f32p]),
 ]
 
 RTH_EXPORTS = [
@@ -192,6 +208,7 @@ RTH_EXPORTS = [
     ("rth_scene_desc", C.POINTER(rtg_scene_desc), [C.c_void_p]),
     ("rth_scene_get_info", C.c_int, [C.c_void_p, C.POINTER(rth_scene_info)]),
     ("rth_scene_permutation", C.c_int, [C.c_void_p, u32p]),
+    ("rth_scene_material_params", C.POINTER(rtg_material_params), [C.c_void_p, u32p]),
     ("rth_save_hdr", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, f32p, C.c_uint32]),
     ("rth_write_hdr", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, f32p]),
     ("rth_read_hdr", C.c_int, [C.c_char_p, i32p, i32p, C.POINTER(f32p)]),

@@ -30,7 +30,8 @@ ARCH = os.environ.get("RTG_ARCH", "gfx950")
 HOST_SRC = ["host/image_io.cpp", "host/jpeg_decode.cpp", "host/gem_json.cpp", "host/scene_front.cpp"]
 DEVICE_SRC = ["device/rtg_trace.hip", "device/rtg_scene.hip", "device/rtg_render.hip", "device/rtg_api.hip",
               "device/rtg_shade.hip", "device/rtg_light.hip", "device/rtg_multi.hip", "device/rtg_bvh.hip",
-              "device/rtg_denoise.hip", "device/rtg_env.hip", "device/rtg_light_pick.hip"]
+              "device/rtg_denoise.hip", "device/rtg_env.hip", "device/rtg_light_pick.hip",
+              "device/rtg_shade_phys.hip"]
 # per-unit compile flags: k_shade's translation unit takes LLVM's max-ilp scheduler, which its
 # latency-bound body prefers, while the traversal keeps the default; the traversal's
 # unit is built without SLP vectorisation, whose packed FP32 pairs in the triangle test held k_trace at
@@ -41,6 +42,8 @@ DEVICE_FLAGS = {"device/rtg_shade.hip": ["-mllvm", "-amdgpu-sched-strategy=max-i
 DEVICE_FLAGS.update({"device/rtg_%s.hip" % u: ["-fno-slp-vectorize"] for u in ("trace", "scene", "render", "api")})
 # k_shade_pick (rtg_set_light_sampling) is k_shade's body: its unit takes k_shade's flags
 DEVICE_FLAGS["device/rtg_light_pick.hip"] = DEVICE_FLAGS["device/rtg_shade.hip"]
+# ... and so is k_shade_phys (rtg_set_material_model)
+DEVICE_FLAGS["device/rtg_shade_phys.hip"] = DEVICE_FLAGS["device/rtg_shade.hip"]
 
 
 def _newer(out, deps):

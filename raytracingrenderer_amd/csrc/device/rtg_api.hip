@@ -130,6 +130,8 @@ int upload_scene(int device, const HostScene& hs, rtg_handle* h) {
     }
     h->cam = hs.cam;
     h->proj = hs.proj;
+    h->tri_mat = hs.tri_mat;
+    h->n_desc_mats = hs.n_desc_mats;
     h->W = (int)hs.cam.width;
     h->H = (int)hs.cam.height;
     HIPOK(hipMalloc((void**)&h->d_film, (size_t)h->W * h->H * 3 * sizeof(float)));
@@ -196,6 +198,8 @@ void rtg_destroy(rtg_handle* h) {
     denoise_release(h);
     (void)hipFree(h->d_env_table);
     (void)hipFree(h->d_light_table);
+    (void)hipFree(h->d_phys);
+    (void)hipFree(h->d_phys_index);
     (void)hipFree(h->d_img);
     (void)hipFree(h->d_nodes); (void)hipFree(h->d_nodesq); (void)hipFree(h->d_leafbox); (void)hipFree(h->d_tris48); (void)hipFree(h->d_shade); (void)hipFree(h->d_mats);
     (void)hipFree(h->d_lights); (void)hipFree(h->d_texinfo); (void)hipFree(h->d_texels); (void)hipFree(h->d_film);

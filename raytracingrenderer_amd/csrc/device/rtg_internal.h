@@ -5,6 +5,7 @@
 #pragma once
 #include "rtg_dev.h"
 #include "../../../include/rtg.h"
+#include "rtg_phys.h"
 
 #include <hip/hip_runtime.h>
 #include <rocprofiler-sdk-roctx/roctx.h>
@@ -66,6 +67,9 @@ using namespace rtgd;
 #endif
 #ifndef RTG_LDS_LIGHTS
 #define RTG_LDS_LIGHTS 48   // ... and the light table up to this many (80 B each): 5 x 48 < 256 threads
+#endif
+#ifndef RTG_LDS_PHYS
+#define RTG_LDS_PHYS 64     // k_shade_phys holds the material parameter table in LDS up to this many (48 B each)
 #endif
 #ifndef RTG_SHADE_WAVES
 #define RTG_SHADE_WAVES 7   // min waves per SIMD for k_shade (72 VGPRs, no spills; one tile per block)
@@ -390,6 +394,18 @@ struct rtg_handle {
     std::vector<uint32_t> light_entries;  // the table's host copy (rtg_light_table)
     std::vector<double> light_weights;    // the weights it was built from (rtg_light_weights)
     double light_build_ms = 0.0;
+    // rtg_set_material_model (rtg_shade_phys.hip): the parameter records of rtg_set_material_params, and
+    // the device table (unique records + one index per triangle) built from them by the first
+    // RTG_MATERIALS_PHYSICAL setting, rebuilt when the parameters change, kept until rtg_destroy
+    int material_model = RTG_MATERIALS_REFERENCE;
+    std::vector<uint32_t> tri_mat;             // [triangle] rtg_scene_desc.material (upload_scene; host only)
+    uint32_t n_desc_mats = 0;                  // rtg_scene_desc.n_materials
+    std::vector<rtg_material_params> mat_params;
+    bool phys_built = false;                   // the device table holds mat_params
+    bool phys_any = false;                     // a triangle has a conductor, plastic or Oren-Nayar record
+    PhysMat* d_phys = nullptr;
+    unsigned* d_phys_index = nullptr;
+    int n_phys = 0;
 };
 #define RTG_CNT_PENDING 0xFFFFFFFFu
 
@@ -417,6 +433,8 @@ struct HostScene {
     float cull_scale = 0.0f;
     DevCamera cam{};
     rtg_camera_proj proj{};
+    std::vector<uint32_t> tri_mat;  // [triangle] rtg_scene_desc.material, before the merge (the physical
+    uint32_t n_desc_mats = 0;       // material model's own index; not uploaded by upload_scene)
 };
 
 // rtg_bvh.hip: the own binary tree with spatial splits over the triangles (descriptor node format)
@@ -485,6 +503,14 @@ int light_sampling_check(const char* who, const rtg_light_sampling* p);
 // one k_shade_pick launch (ALT, TAB; ENV = env with a table) for bounce b
 int launch_shade_pick(bool alt, bool tab, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
                       const PathBufs& p, int b, const EnvTable& env, const LightPick& pick);
+// rtg_shade_phys.hip: the table k_shade_phys shades from under the handle's setting and integrator, or
+// one with a null pointer (the reference model: today's launches)
+PhysArgs phys_args_of(const rtg_handle* h);
+// one k_shade_phys launch (ALT, TAB; the environment table and the light pick as runtime arguments)
+int launch_shade_phys(bool alt, bool tab, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
+                      const PathBufs& p, int b, const EnvTable& env, const LightPick& pick, const PhysArgs& phys);
+// RTG_ERR_ARG (with "who: ..." as the message) for records outside include/rtg.h's ranges
+int material_params_check(const char* who, const rtg_material_params* params, uint32_t n, uint32_t n_materials);
 // rtg_shade.hip: one k_shade launch of `grid` blocks (ALT = alt, TAB = tab) for bounce b
 // (env with a table: k_shade_env, the ALT kernel with the environment light's alias-table sample)
 int launch_shade(bool alt, bool tab, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,

@@ -508,6 +508,33 @@ int rtg_group_set_light_sampling(rtg_group* g, const rtg_light_sampling* p) {
     return RTG_OK;
 }
 
+int rtg_group_set_material_params(rtg_group* g, const rtg_material_params* params, uint32_t n) {
+    if (!g) { g_err = "rtg_group_set_material_params: null group"; return RTG_ERR_ARG; }
+    // checked once for all ranks, so an argument error leaves every rank's records as they were
+    for (rtg_handle* h : g->h)
+        if (int rc = material_params_check("rtg_group_set_material_params", params, n, h->n_desc_mats)) return rc;
+    for (rtg_handle* h : g->h)
+        if (int rc = rtg_set_material_params(h, params, n)) return rc;
+    return RTG_OK;
+}
+
+int rtg_group_set_material_model(rtg_group* g, int mode) {
+    if (!g) { g_err = "rtg_group_set_material_model: null group"; return RTG_ERR_ARG; }
+    for (rtg_handle* h : g->h) {
+        int prev = RTG_MATERIALS_REFERENCE;
+        (void)rtg_get_material_model(h, &prev);
+        const int rc = rtg_set_material_model(h, mode);
+        if (rc) {
+            for (rtg_handle* u : g->h) {
+                if (u == h) break;
+                (void)rtg_set_material_model(u, prev);
+            }
+            return rc;
+        }
+    }
+    return RTG_OK;
+}
+
 int rtg_group_render(rtg_group* g, uint32_t first_sample, uint32_t n_samples, uint64_t seed) {
     if (!g) return RTG_ERR_ARG;
     g->reduced = false;

@@ -620,7 +620,10 @@ static int issue_chunk(rtg_handle* h, ChunkSlot& sl, const ChunkArgs& a, int max
                 const bool alt = h->integrator != RTG_INTEGRATOR_PATH;
                 const EnvTable et = env_table_of(h);  // RTG_ENV_LUMINANCE with a table: k_shade_env
                 const LightPick pk = light_pick_of(h);  // RTG_LIGHTS_POWER with a table: k_shade_pick
-                if (pk.table) rc = launch_shade_pick(alt, tab, 8 * tiles, ss, h->sv, a, pb, b - 1, et, pk);
+                const PhysArgs ph = phys_args_of(h);  // RTG_MATERIALS_PHYSICAL with such a material: k_shade_phys
+                if (ph.table)
+                    rc = launch_shade_phys(alt, tab && ph.n <= RTG_LDS_PHYS, 8 * tiles, ss, h->sv, a, pb, b - 1, et, pk, ph);
+                else if (pk.table) rc = launch_shade_pick(alt, tab, 8 * tiles, ss, h->sv, a, pb, b - 1, et, pk);
                 else rc = launch_shade(alt, tab, 8 * tiles, ss, h->sv, a, pb, b - 1, &et);
                 if (rc) return rc;
                 timed_end(h, ss, kinds, 2);

@@ -514,5 +514,7 @@ int prepare_scene(const rtg_scene_desc* d, HostScene& hs) {
     hs.cam.width = d->camera.width;
     hs.cam.height = d->camera.height;
     hs.proj = d->projection;
+    hs.tri_mat.assign(d->material, d->material + nt);
+    hs.n_desc_mats = d->n_materials;
     return RTG_OK;
 }

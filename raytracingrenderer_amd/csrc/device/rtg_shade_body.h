@@ -12,12 +12,24 @@
 // RTG_LIGHTS_POWER: two draws r0, d1 in place of the uniform pick's one) with the entry's pmf in
 // s.pmf's place, at the three sites that draw li or read s.pmf. k_shade and k_shade_env set PICK =
 // false and keep their instructions.
+// RTG_SHADE_PHYS defined (k_shade_phys, rtg_shade_phys.hip; the including kernel also sets the PhysArgs
+// pm, and ENV and PICK as run-time constants): conductor, plastic and Oren-Nayar records shade with
+// rtg_phys.h's models (rtg_set_material_model, RTG_MATERIALS_PHYSICAL). The parameter record comes from a
+// table of its own, indexed by the hit's triangle id (a load beside the shading record's, not after it);
+// NEE evaluates the model in albedo / pi's place; the bounce samples it, and "specular" becomes a
+// property of the sample, not of the material. Without the macro the preprocessor leaves the other
+// kernels the text they had.
     __shared__ unsigned s_cnt[2][RTG_TB / 64];
     __shared__ unsigned s_base[2];
     __shared__ float4 s_sho[RTG_TB], s_shd[RTG_TB];  // NEE ray staged until its queue position is known
     __shared__ DevMat s_mat[TAB ? RTG_LDS_MATS : 1];
     __shared__ DevLight s_lt[TAB ? RTG_LDS_LIGHTS : 1];
+#ifdef RTG_SHADE_PHYS
+    __shared__ uint4 s_pk[TAB ? RTG_LDS_LIGHTS : 1];
+    __shared__ PhysMat s_pm[TAB ? RTG_LDS_PHYS : 1];  // the material parameter table (three pieces per record)
+#else
     __shared__ uint4 s_pk[(PICK && TAB) ? RTG_LDS_LIGHTS : 1];  // the light-pick table (one entry per light)
+#endif
     const int lane = lane_id();
     const int wave = threadIdx.x >> 6;
     const bool lean0 = b == 0;  // bounce 0: path id = position, camera origin, thr 1, PCG seed, canHitLight
@@ -55,6 +67,11 @@
                                              (lptr_t)(reinterpret_cast<float4*>(s_lt) + w0), 16, 0, 0);
         if (PICK && (int)threadIdx.x < s.n_lights)  // n_lights <= RTG_LDS_LIGHTS < 64: wave 0's lanes
             __builtin_amdgcn_global_load_lds((gptr_t)(lpk.table + threadIdx.x), (lptr_t)(s_pk + w0), 16, 0, 0);
+#ifdef RTG_SHADE_PHYS
+        if ((int)threadIdx.x < 3 * pm.n)  // pm.n <= RTG_LDS_PHYS: at most 192 pieces
+            __builtin_amdgcn_global_load_lds((gptr_t)(reinterpret_cast<const float4*>(pm.table) + threadIdx.x),
+                                             (lptr_t)(reinterpret_cast<float4*>(s_pm) + w0), 16, 0, 0);
+#endif
     }
     // one 256-path tile per block: a finished block frees its slot for the next tile
     {
@@ -69,6 +86,9 @@
         // the payload and, on a hit, the triangle's shading record (issued before the tables' barrier)
         float4 ro = make_float4(a.cam.ox, a.cam.oy, a.cam.oz, 0.0f), rd = ro, h = ro;
         DevShade S;
+#ifdef RTG_SHADE_PHYS
+        unsigned pmi = 0;  // the hit triangle's parameter record
+#endif
         if (valid) {
             unsigned j = i;  // bounce 0: the pixel's camera ray and first hit (k_generate), shared by its samples
             if (lean0 && !a.cam_mode) {  // (per-sample camera rays, k_generate_sampled: the path's own)
@@ -79,6 +99,9 @@
             rd = in_d[j];
             h = p.hits[j];
             if (h.x < RTG_FLT_MAX) S = s.shade[__float_as_int(h.y)];
+#ifdef RTG_SHADE_PHYS
+            if (h.x < RTG_FLT_MAX) pmi = pm.index[__float_as_int(h.y)];
+#endif
         }
         if (TAB) {
             // global_load_lds completes on vmcnt, not on the barrier: wait for it explicitly (the
@@ -106,6 +129,9 @@
             v3 env_dir = d, x = o, sn = d, alb = d, l_p2 = o, l_em = d;
             float l_g = 0.0f, l_pdf = 0.0f;
             float l_pp = 0.0f;  // PICK: the picked light's pmf * l_pdf (one value across the lookup, not two)
+#ifdef RTG_SHADE_PHYS
+            int ptag = RTG_MODEL_REFERENCE;  // the hit's model tag (stage 1)
+#endif
             if (ALT && a.mode == RTG_INTEGRATOR_DIRECT_MIS && b == 1) {
                 // computeDirectMIS, second half (Renderer.h:520-553): the BSDF-sampled ray's hit.
                 // thr = (bsdf value, bsdf pdf); scratch planes 2/3 = (x, light pdf * pmf) and
@@ -264,7 +290,14 @@
                     spec = M.kind == RTG_MAT_MIRROR || M.kind == RTG_MAT_GLASS;
                     // albedo->sample(tu, tv): one fetch for BSDF::evaluate (NEE) and BSDF::sample
                     alb = tex_sample(s, M, tu, tv);
+#ifdef RTG_SHADE_PHYS
+                    // a delta conductor takes no light sample; a plastic's base always does
+                    const PhysMat& Q0 = TAB ? s_pm[pmi] : pm.table[pmi];
+                    ptag = __float_as_int(Q0.a.x);
+                    if (!spec && !(ptag == RTG_MODEL_CONDUCTOR && Q0.a.y < RTG_ALPHA_DELTA)) {
+#else
                     if (!spec) {
+#endif
                         const int nl = s.n_lights;
                         float pmf = 0.0f;
                         int li;
@@ -326,6 +359,9 @@
                 const DevMat& M = TAB ? s_mat[mid] : s.mats[mid];
                 const v3 wo = neg(d);
                 const frame fr = frame_from(sn);
+#ifdef RTG_SHADE_PHYS
+                const PhysMat& Q = TAB ? s_pm[pmi] : pm.table[pmi];
+#endif
                 // ---- computeDirect (Renderer.h:423-473), after the light sample above
                 v3 ld = mk(0.0f, 0.0f, 0.0f);
                 bool ld_pre = false;  // contrib takes the visible NEE value now
@@ -338,7 +374,12 @@
                     const float maxt = sqrtf(length_sq(sd)) - (2.0f * RTG_EPS);
                     sd = normalize(sd);
                     const v3 so = add(x, muls(sd, RTG_EPS));
+#ifdef RTG_SHADE_PHYS
+                    const v3 f = ptag != RTG_MODEL_REFERENCE ? phys_eval(Q, alb, to_local(fr, wo), to_local(fr, sd))
+                                                            : divs_pi(alb);
+#else
                     const v3 f = divs_pi(alb);  // BSDF::evaluate
+#endif
                     ld = divs(muls(mul(f, emitted), l_g), PICK ? l_pp : pmf * l_pdf);
                     const v3 cvis = mul(thr, ld);
                     s_sho[threadIdx.x] = make_float4(so.x, so.y, so.z, maxt);
@@ -363,6 +404,29 @@
                         v3 ind;
                         float pdf;
                         PcgSampler smp{st, inc};
+#ifdef RTG_SHADE_PHYS
+                        // the sample says whether it is specular (a delta lobe) and whether the path lives
+                        bool sp = spec, live = true;
+                        v3 wi;
+                        if (ptag != RTG_MODEL_REFERENCE) {
+                            wi = to_world(fr, phys_sample(Q, alb, to_local(fr, wo), smp, ind, pdf, sp));
+                            live = pdf > 0.0f;
+                        } else {
+                            wi = bsdf_sample(M.kind, M.int_ior, M.ext_ior, alb, fr, wo, smp, ind, pdf);
+                        }
+                        st = smp.s;
+                        if (live) {
+                            if (sp) thr = divs(mul(thr, ind), pdf);
+                            else thr = divs(muls(mul(thr, ind), fabsf(dot(wi, sn))), pdf);
+                            const v3 no = add(x, muls(wi, RTG_EPS));
+                            n_o = make_float4(no.x, no.y, no.z, __int_as_float(pid));
+                            n_d = make_float4(wi.x, wi.y, wi.z, sp ? 1.0f : 0.0f);  // canHitLight
+                            want_ext = true;
+                            n_t = make_float4(thr.x, thr.y, thr.z, 0.0f);
+                            n_r = st;
+                            nterms = (b + 1) | ((sp ? 1 : 0) << 8);
+                        }
+#else
                         const v3 wi = bsdf_sample(M.kind, M.int_ior, M.ext_ior, alb, fr, wo,
                                                   smp, ind, pdf);
                         st = smp.s;
@@ -375,6 +439,7 @@
                         n_t = make_float4(thr.x, thr.y, thr.z, 0.0f);
                         n_r = st;
                         nterms = (b + 1) | ((spec ? 1 : 0) << 8);
+#endif
                     }
                 }
             }

@@ -31,6 +31,10 @@
 // reference's Scene::sampleLight; power: lights picked by emitted power through an alias table) and
 // -lightUniformShare x (the share of the uniform pick mixed in, default 0.125), for one device and for
 // -gpus / -devices alike.
+// Material model (rtg_set_material_model): -materials reference|physical (reference: conductor, plastic
+// and Oren-Nayar materials shade as the reference's Lambertian stubs; physical: GGX conductor, coated
+// plastic and Oren-Nayar from the scene's own roughness, eta, k, IORs and alpha), for one device and for
+// -gpus / -devices alike.
 // Multi-GPU (one node): -gpus N renders on devices 0..N-1, -devices a,b,... on a list. Rank r
 // renders the 32x32 tiles with (tile_x + tile_y) % N == r, and the film is assembled on the first
 // device from every device's own tiles (packed, one RCCL send per device, scattered) before it is
@@ -115,6 +119,11 @@ int main(int argc, char** argv) {
     if (lsn != "uniform" && lsn != "power") return die("-lightSampling", "one of uniform, power");
     lsm.mode = lsn == "power" ? RTG_LIGHTS_POWER : RTG_LIGHTS_UNIFORM;
     lsm.uniform_share = std::stof(get("-lightUniformShare", "0.125"));
+    const std::string mtl = get("-materials", "reference");
+    if (mtl != "reference" && mtl != "physical") return die("-materials", "one of reference, physical");
+    const bool physical = mtl == "physical";
+    uint32_t n_params = 0;
+    const rtg_material_params* params = rth_scene_material_params(scene, &n_params);
     rtg_handle* rt = nullptr;
     rtg_group* grp = nullptr;
     if (devices.empty()) {
@@ -123,6 +132,9 @@ int main(int argc, char** argv) {
         if (rtg_set_camera_sampling(rt, &cs) != 0) return die("rtg_set_camera_sampling", rtg_last_error());
         if (rtg_set_env_sampling(rt, env_mode) != 0) return die("rtg_set_env_sampling", rtg_last_error());
         if (rtg_set_light_sampling(rt, &lsm) != 0) return die("rtg_set_light_sampling", rtg_last_error());
+        if (physical && (rtg_set_material_params(rt, params, n_params) != 0 ||
+                         rtg_set_material_model(rt, RTG_MATERIALS_PHYSICAL) != 0))
+            return die("rtg_set_material_model", rtg_last_error());
     } else {
         if (rtg_group_create(devices.data(), (int)devices.size(), rth_scene_desc(scene), &grp) != 0)
             return die("rtg_group_create", rtg_last_error());
@@ -130,6 +142,9 @@ int main(int argc, char** argv) {
         if (rtg_group_set_camera_sampling(grp, &cs) != 0) return die("rtg_group_set_camera_sampling", rtg_last_error());
         if (rtg_group_set_env_sampling(grp, env_mode) != 0) return die("rtg_group_set_env_sampling", rtg_last_error());
         if (rtg_group_set_light_sampling(grp, &lsm) != 0) return die("rtg_group_set_light_sampling", rtg_last_error());
+        if (physical && (rtg_group_set_material_params(grp, params, n_params) != 0 ||
+                         rtg_group_set_material_model(grp, RTG_MATERIALS_PHYSICAL) != 0))
+            return die("rtg_group_set_material_model", rtg_last_error());
         std::printf("%d devices, own-tile film exchange by %s\n", (int)devices.size(),
                     rtg_group_uses_rccl(grp) ? "RCCL (ncclSend/ncclRecv)"
                     : devices.size() == 1    ? "none (one device)"

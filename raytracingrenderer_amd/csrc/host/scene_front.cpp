@@ -87,6 +87,7 @@ struct rth_scene {
     std::vector<float> node_bounds;
     std::vector<int32_t> node_links;
     std::vector<rtg_material> materials;
+    std::vector<rtg_material_params> mat_params;  // what the BSDF constructors take, one per material
     std::vector<rth::TexData> tex;
     std::vector<rtg_texture> textures;
     std::vector<int32_t> lights;
@@ -335,12 +336,35 @@ static bool load_scene(const std::string& dir, const rth_load_options& o, rth_sc
             std::fprintf(stderr, "Error in loading\n");
             continue;
         }
+        // the constructors' arguments (SceneLoader.h:117-171, Materials.h:216, 333, 378), kept beside the
+        // material record for rtg_set_material_params; the record itself keeps only its kind
+        rtg_material_params mp{};
+        if (bsdf == "conductor") {
+            mp.model = RTG_MODEL_CONDUCTOR;
+            inst.material.find("eta").as_vec3(mp.eta[0], mp.eta[1], mp.eta[2]);
+            inst.material.find("k").as_vec3(mp.k[0], mp.k[1], mp.k[2]);
+            mp.alpha = 1.62142f * sqrtf(inst.material.find("roughness").as_float(1.0f));
+        } else if (bsdf == "plastic") {
+            mp.model = RTG_MODEL_PLASTIC;
+            mp.int_ior = m.int_ior;
+            mp.ext_ior = m.ext_ior;
+            mp.alpha = 1.62142f * sqrtf(inst.material.find("roughness").as_float(1.0f));
+        } else if (bsdf == "orennayar") {
+            mp.model = RTG_MODEL_ORENNAYAR;
+            mp.sigma = inst.material.find("alpha").as_float(1.0f);
+        } else if (bsdf == "dielectric" && m.kind == RTG_MAT_LAMBERT) {
+            // the rough DielectricBSDF's arguments, kept although no model uses them (it stays the stub)
+            mp.int_ior = m.int_ior;
+            mp.ext_ior = m.ext_ior;
+            mp.alpha = 1.62142f * sqrtf(inst.material.find("roughness").as_float(1.0f));
+        }
         if (m.kind != RTG_MAT_GLASS) { m.int_ior = 0; m.ext_ior = 0; }
         m.texture = texture(dir + "/" + refl);
         if (inst.material.find("emission").str() != "")
             inst.material.find("emission").as_vec3(m.emission[0], m.emission[1], m.emission[2]);
         uint32_t mat_index = (uint32_t)s->materials.size();
         s->materials.push_back(m);
+        s->mat_params.push_back(mp);
 
         M4 xf;
         std::memcpy(xf.m, inst.world, sizeof(xf.m));
@@ -535,6 +559,12 @@ int rth_scene_get_info(const rth_scene* s, rth_scene_info* out) {
     if (!s || !out) return RTG_ERR_ARG;
     *out = s->info;
     return RTG_OK;
+}
+
+const rtg_material_params* rth_scene_material_params(const rth_scene* s, uint32_t* n) {
+    if (!s) return nullptr;
+    if (n) *n = (uint32_t)s->mat_params.size();
+    return s->mat_params.data();
 }
 
 int rth_scene_permutation(const rth_scene* s, uint32_t* out) {

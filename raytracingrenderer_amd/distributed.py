@@ -137,13 +137,15 @@ def reduce_film(film_tensor, dist, dst=0):
 
 
 def render_sharded(rt, n_samples, rank, world, dist=None, film_tensor=None, first_sample=0, exchange=None,
-                   camera_sampling=None):
+                   camera_sampling=None, material_model=None):
     """Render this rank's tiles with RayTracer `rt`, then assemble the film on rank 0.
 
     camera_sampling: a dict of RayTracer.set_camera_sampling's arguments (e.g. {"filter": "tent"}),
     applied to this rank's tracer before it renders; every rank must pass the same one (the camera
     stream is keyed by pixel and sample, so the ranks' tiles then fit together as on one device).
     None leaves the tracer's setting as it is.
+    material_model: "reference" or "physical" (RayTracer.set_material_model), applied likewise; every
+    rank must pass the same one. None leaves the tracer's setting as it is.
 
     world > 1: rank 0's film_tensor (torch float32 HxWx3) receives the whole film from every rank's
     own tiles (FilmExchange; pass `exchange` to reuse its buffers across calls); a CUDA tensor is
@@ -154,6 +156,8 @@ def render_sharded(rt, n_samples, rank, world, dist=None, film_tensor=None, firs
     tiles = tiles_for_rank(rt.width, rt.height, rank, world)
     if camera_sampling is not None:
         rt.set_camera_sampling(**camera_sampling)
+    if material_model is not None:
+        rt.set_material_model(material_model)
     rt.render(n_samples, tiles=tiles, first_sample=first_sample)
     if film_tensor is None:
         if world > 1:

@@ -82,6 +82,15 @@ class Scene:
     def materials(self):
         return [self.desc.materials[i] for i in range(self.desc.n_materials)]
 
+    @property
+    def material_params(self):
+        """What the reference's loader hands the BSDF constructors, one rtg_material_params per entry of
+        `materials` in that order (rth_scene_material_params): model tag, alpha = 1.62142f *
+        sqrtf(roughness), sigma, eta, k, int_ior, ext_ior. RayTracer.set_material_model passes them on."""
+        n = C.c_uint32()
+        p = N.rth().rth_scene_material_params(self._h, C.byref(n))
+        return [N.rtg_material_params.from_buffer_copy(p[i]) for i in range(n.value)]  # (copies: they outlive the scene)
+
     def texture(self, i):
         t = self.desc.textures[i]
         return self._view(t.texels, t.width * t.height * 3, np.float32).reshape(t.height, t.width, 3)
@@ -238,6 +247,56 @@ def _light_sampling(mode, uniform_share):
     return N.rtg_light_sampling(int(mode), float(uniform_share))
 
 
+MATERIAL_MODELS = {"reference": N.RTG_MATERIALS_REFERENCE, "physical": N.RTG_MATERIALS_PHYSICAL}
+MODEL_TAGS = {"conductor": N.RTG_MODEL_CONDUCTOR, "plastic": N.RTG_MODEL_PLASTIC, "orennayar": N.RTG_MODEL_ORENNAYAR}
+
+
+def _material_model(mode):
+    """The RTG_MATERIALS_* value of set_material_model's argument (a name of MATERIAL_MODELS or a value;
+    an unknown value is the library's error)."""
+    if isinstance(mode, str):
+        if mode not in MATERIAL_MODELS:
+            raise ValueError("unknown material model %r (one of %s)" % (mode, ", ".join(MATERIAL_MODELS)))
+        return MATERIAL_MODELS[mode]
+    return int(mode)
+
+
+def _material_params_array(params):
+    """A ctypes array of rtg_material_params from a sequence of them."""
+    params = list(params)
+    return (N.rtg_material_params * max(len(params), 1))(*params), len(params)
+
+
+def material_params_check(params, n_materials):
+    """rtg_set_material_params' argument check alone (rtg_material_params_check; no GPU): raises
+    NativeError for a wrong count, an unknown tag or a negative or non-finite parameter."""
+    arr, n = _material_params_array(params)
+    lib = N.rtg()
+    _check(lib.rtg_material_params_check(arr, n, n_materials), lib.rtg_last_error)
+
+
+def material_probe(model, wo, draws, query, alpha=0.0, sigma=0.0, int_ior=1.33, ext_ior=1.0, eta=(0.0, 0.0, 0.0),
+                   k=(0.0, 0.0, 0.0), albedo=(1.0, 1.0, 1.0), normal=(0.0, 0.0, 1.0)):
+    """The physical material kernels' own sample / evaluate / PDF (rtg_probe_material, test surface) on
+    the current device. model: a name of MODEL_TAGS or a tag; wo (n, 3), draws (n, 3) and query (n, 3)
+    per case, world space, with one parameter set, albedo and shading normal for all. Returns a dict:
+    "wi" (n, 3), "colour" (n, 3), "pdf", "draws", "delta" (n,), "evaluate" (n, 3), "PDF" (n,)."""
+    tag = MODEL_TAGS[model] if isinstance(model, str) else int(model)
+    wo, dr, qi = (np.ascontiguousarray(v, np.float32).reshape(-1, 3) for v in (wo, draws, query))
+    if not len(wo) == len(dr) == len(qi):
+        raise ValueError("material_probe: wo, draws and query must have one length")
+    c = np.zeros((len(wo), 28), np.float32)
+    c[:, 0:5] = (tag, alpha, sigma, int_ior, ext_ior)
+    c[:, 5:8], c[:, 8:11], c[:, 11:14], c[:, 14:17] = eta, k, albedo, normal
+    c[:, 17:20], c[:, 20:23], c[:, 23:26] = wo, dr, qi
+    out = np.zeros((len(wo), 16), np.float32)
+    lib = N.rtg()
+    _check(lib.rtg_probe_material(N.ptr(c, C.c_float), len(c), N.ptr(out, C.c_float)), lib.rtg_last_error)
+    return {"wi": out[:, 0:3].copy(), "colour": out[:, 3:6].copy(), "pdf": out[:, 6].copy(),
+            "draws": out[:, 7].astype(np.int32), "delta": out[:, 8] != 0, "evaluate": out[:, 9:12].copy(),
+            "PDF": out[:, 12].copy()}
+
+
 class RayTracer:
     """RayTracer (Renderer.h:31-899) backed by librtg on one GPU."""
 
@@ -389,6 +448,31 @@ class RayTracer:
         u = e.view(np.uint32)
         return {"prob": e[:, 0].copy(), "alias": u[:, 1].copy(), "pmf_self": e[:, 2].copy(),
                 "pmf_alias": e[:, 3].copy(), "entries": u.copy(), "weights": wt, "build_ms": ms.value}
+
+    def set_material_model(self, mode="reference"):
+        """How conductor, plastic and Oren-Nayar materials shade (rtg_set_material_model). "reference"
+        (default): as RTBase's stubs do, a cosine-sampled Lambertian, the reference's films bit for bit.
+        "physical": a GGX conductor with the material's eta and k, a dielectric GGX coat over the diffuse
+        base, and the qualitative Oren-Nayar model (include/rtg.h has the definition); a lobe narrower
+        than RTG_ALPHA_DELTA reflects as a mirror. The scene's own parameters (Scene.material_params) are
+        handed to the library here. Applies to render(), adaptiveRender() and the "path" and "direct"
+        integrators; "direct_mis", "albedo", "normals", lightTracer(), instantRadiosity() and the
+        denoiser's guides keep the reference model. A scene without such a material renders the same
+        film under both."""
+        m = _material_model(mode)
+        if m == N.RTG_MATERIALS_PHYSICAL and not getattr(self, "_material_params_set", False):
+            arr, n = _material_params_array(self.scene.material_params)
+            _check(self._lib.rtg_set_material_params(self._h, arr, n), self._lib.rtg_last_error)
+            self._material_params_set = True
+        _check(self._lib.rtg_set_material_model(self._h, m), self._lib.rtg_last_error)
+
+    def material_model(self):
+        """The current setting, "reference" or "physical"."""
+        m = C.c_int()
+        _check(self._lib.rtg_get_material_model(self._h, C.byref(m)), self._lib.rtg_last_error)
+        return {v: k for k, v in MATERIAL_MODELS.items()}.get(m.value, m.value)
+
+    material_probe = staticmethod(material_probe)
 
     def light_records(self):
         """The light records as uploaded (rtg_light_records): (n_lights, 20) float32 = v0.xyz area |
@@ -630,6 +714,15 @@ class RayTracerGroup:
         """RayTracer.set_light_sampling on every rank (rtg_group_set_light_sampling)."""
         p = _light_sampling(mode, uniform_share)
         _check(self._lib.rtg_group_set_light_sampling(self._g, C.byref(p)), self._lib.rtg_last_error)
+
+    def set_material_model(self, mode="reference"):
+        """RayTracer.set_material_model on every rank (rtg_group_set_material_params / _model)."""
+        m = _material_model(mode)
+        if m == N.RTG_MATERIALS_PHYSICAL and not getattr(self, "_material_params_set", False):
+            arr, n = _material_params_array(self.scene.material_params)
+            _check(self._lib.rtg_group_set_material_params(self._g, arr, n), self._lib.rtg_last_error)
+            self._material_params_set = True
+        _check(self._lib.rtg_group_set_material_model(self._g, m), self._lib.rtg_last_error)
 
     def setup_ms(self):
         """(host build of the device records, parallel uploads) of rtg_group_create, in ms."""

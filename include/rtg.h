@@ -42,7 +42,8 @@ extern "C" {
  *    rtg_*_camera_sampling and rtg_probe_camera_samples; environment light sampling,
  *    rtg_*_env_sampling, rtg_env_* and rtg_probe_env_samples; rtg_probe_connect; light selection,
  *    rtg_*_light_sampling, rtg_light_* and rtg_probe_light_pick; the material model,
- *    rtg_*_material_model, rtg_*_material_params and rtg_probe_material) */
+ *    rtg_*_material_model, rtg_*_material_params and rtg_probe_material; path-tracer MIS,
+ *    rtg_*_path_mis, rtg_probe_mis_weight, rtg_probe_env_pdf and rtg_light_of_triangle) */
 #define RTG_ABI_VERSION 6
 
 /* error codes */
@@ -451,7 +452,7 @@ int  rtg_light_pick_build(const double* weights, uint32_t n, double uniform_shar
  *                  from the sampled wi.
  *   delta lobes    a GGX lobe with alpha < RTG_ALPHA_DELTA is a delta lobe (coffee's plastics have
  *                  roughness 0). The path tracer counts an emitter hit only after a camera or specular
- *                  bounce and has no MIS, so a lobe that narrow lit by NEE alone would be all fireflies.
+ *                  bounce and by default has no MIS, so a lobe that narrow lit by NEE alone would be all fireflies.
  *                  A delta lobe is left out of evaluate, PDF and NEE; a ray sampled from it reflects about
  *                  the normal, wi = (-wo.x, -wo.y, wo.z), carries canHitLight = 1 and skips the cosine
  *                  factor, as MirrorBSDF does. Conductor: colour = albedo F_c(clamp01(wo.z)), pdf = 1, no
@@ -473,7 +474,8 @@ int  rtg_light_pick_build(const double* weights, uint32_t n, double uniform_shar
  * Oren-Nayar record: a scene without one keeps today's kernels and bits under both settings. It does not
  * apply to RTG_INTEGRATOR_DIRECT_MIS, _ALBEDO and _NORMALS, to rtg_render_light and
  * rtg_render_instant_radiosity, or to the denoiser's guides: they keep the reference model. Not modelled:
- * rough dielectric transmission, LayeredBSDF, MIS between NEE and BSDF-sampled emitter hits.
+ * rough dielectric transmission, LayeredBSDF. (MIS between NEE and BSDF-sampled emitter hits is
+ * rtg_set_path_mis, below; RTG_ALPHA_DELTA and the delta-lobe rule are the same under it.)
  * rtg_set_material_params copies n records (n must equal rtg_scene_desc.n_materials);
  * rtg_material_params_check is its argument check alone (no handle, no device call): a null pointer, a
  * wrong n, an unknown tag, or an alpha, sigma, eta, k, int_ior or ext_ior that is negative or not finite
@@ -507,6 +509,85 @@ int  rtg_get_material_model(rtg_handle* h, int* mode);
  * out: n*16 floats (wi.xyz world, colour.rgb, pdf, draws consumed, delta flag, evaluate(query).rgb,
  * PDF(query), pad[3]). A model other than conductor, plastic or Oren-Nayar: RTG_ERR_ARG. */
 int  rtg_probe_material(const float* cases, uint32_t n, float* out);
+
+/* ---- multiple importance sampling of emitters in the path tracer (rtg_shade_mis.hip,
+ * rtg_mis.h). pathTrace (Renderer.h:328-392) counts an emitter hit only after a camera or specular bounce,
+ * so after any other bounce NEE alone lights the vertex, and on a miss it returns
+ * background->evaluate(r.dir) without the path throughput at any depth (:390), so with the environment in
+ * the light list it is counted twice after a diffuse bounce, once unweighted. That is the default here,
+ * RTG_PATH_MIS_OFF, untouched: the same kernels, draws and bits. RTG_PATH_MIS_POWER combines the NEE
+ * sample and the BSDF sample of every non-specular vertex with the power heuristic, and weighs a miss by
+ * the throughput: it DELIBERATELY DEPARTS from Renderer.h:390, and is the project's correct path
+ * estimator under an environment light. On a scene whose environment is not a light and whose emissive
+ * triangles are all in the light list both settings have the same expectation; on an environment-lit
+ * scene they do not, and the default is the one that is off. Definition, IEEE float32 in the order
+ * written, no contraction:
+ *   the path     draws exactly what PATH draws, in the same order (light pick, light sample, Russian
+ *                roulette, BSDF sample; no other random numbers), so a film follows the paths of the PATH
+ *                film of the same seed and only the weights differ.
+ *   mis_w(p, q)  r = q / p; w = 1 / (1 + (r r)): the power heuristic with beta = 2 for a sample of density
+ *                p against a technique of density q, in a form that cannot come to inf / inf for a finite
+ *                p > 0. A w that is not a number (both densities 0, or both infinite) is 0.5, on both
+ *                sides of the pair.
+ *   NEE          at a non-specular vertex whose light sample has g > 0, computeDirect's Ld = f E g /
+ *                (pmf pdf) is multiplied on every channel by mis_w(p_l, p_b). Area light:
+ *                p_l = convertPDFAreaToSolidAngle(pmf pdf, l2, cos_l) = cos_l > 0 ? ((pmf pdf) l2) / cos_l
+ *                : 0, with l2 and cos_l the squared distance and the light's cosine that form g.
+ *                Environment light: p_l = pmf pdf. pmf is the pick's (1 / n_lights, or the table entry's
+ *                under RTG_LIGHTS_POWER). p_b = BSDF::PDF(wo, sd), sd the shadow ray's direction
+ *                normalize(p2 - x): cosineHemispherePDF (dot(sd, frame.w) >= 0 ? that / M_PI in binary64 :
+ *                0) for a reference-kind record, PDF(wo, sd) of the material model above for a physical
+ *                one (for a plastic with a delta coat: the base's share, (1 - ps) (wi.z / M_PI)).
+ *   BSDF sample  its solid-angle pdf travels to the next vertex (path payload thr.w); a specular or delta
+ *                sample carries canHitLight and weight 1, as does the camera ray. A sample whose pdf is not
+ *                > 0 (a cosine sample on the horizon, wi.z = 0) ends the path at this vertex (its NEE term
+ *                stays), for a reference-kind record as the material model's guard does for a physical
+ *                one: PATH carries the throughput 0 / 0 on, which only a later visible NEE sample shows,
+ *                while this mode's thr E on a miss would show it every time.
+ *   emitter hit  with canHitLight: thr emission, as PATH. Otherwise, with i the hit triangle's index in
+ *                the light list, L its light record, t the hit distance, d the ray's direction and
+ *                cos_l = max(-dot(d, L.gNormal), 0): cos_l > 0: (thr emission) mis_w(p_b, p_l),
+ *                p_l = convertPDFAreaToSolidAngle(pmf_i (1 / area_i), t t, cos_l), pmf_i = 1 / n_lights or
+ *                entry i's own pmf under RTG_LIGHTS_POWER; the back side (cos_l = 0): 0, as PATH gives,
+ *                for NEE cannot reach it either. An emissive triangle that is not in the light list
+ *                contributes thr emission: no NEE sample can ever reach it. A triangle listed twice counts
+ *                as its first entry.
+ *   miss         bounce 0: E = background->evaluate(d). After a specular or delta sample: thr E. After
+ *                any other sample: (thr E) mis_w(p_b, pmf_env p_env(d)) when the environment is in the
+ *                light list (pmf_env as pmf_i), thr E when it is not.
+ *   p_env(d)     RTG_ENV_UNIFORM (or no table): 1 / (4 pi), uniformSpherePDF. RTG_ENV_LUMINANCE: with
+ *                (u, v) EnvironmentMap::evaluate's own coordinates of d (atan2f(d.z, d.x), plus 2 pi in
+ *                binary64 when negative, over 2 pi; acosf(d.y) over pi), fx = floorf(u w), fy = floorf(v h),
+ *                the cell (cx, cy) = (fx, fy) clamped to [0, w - 1] x [0, h - 1] (not a number: 0), cp that
+ *                cell's own cellpdf (word 2 of entry cy w + cx), st = sqrtf((d.x d.x) + (d.z d.z)):
+ *                !(st > 0) ? 0 : cp / st. For a direction the sampler produced from in-cell draws away
+ *                from the cell's edges this is the sampler's own pdf up to the rounding of st (a few units
+ *                in the last place).
+ * The setting applies to rtg_render, rtg_render_async, rtg_render_adaptive and the group calls under
+ * RTG_INTEGRATOR_PATH only (kernels of their own, k_shade_mis; the default's are not touched), with either
+ * environment mode, light selection mode and material model and with camera sampling. It does not apply
+ * to RTG_INTEGRATOR_DIRECT, _DIRECT_MIS, _ALBEDO and _NORMALS, to rtg_render_light and
+ * rtg_render_instant_radiosity, or to the denoiser's guides: they keep today's kernels and bits under
+ * either setting. Not covered: rough dielectric transmission, LayeredBSDF, per-shading-point light
+ * selection, a lower RTG_ALPHA_DELTA. The setter first issues and waits for queued frames; an unknown
+ * mode is RTG_ERR_ARG, reported before any device call, with the setting and the film left as they were
+ * (rtg_path_mis_check is that check alone). The triangle -> light map (int32 per triangle, -1: no light)
+ * is built on the host from the light list when the mode is first switched on and kept until
+ * rtg_destroy; on the device it stands beside the triangle's parameter record index (one 8-byte load by
+ * the hit's triangle id, beside its shading record), so it is uploaded again when rtg_set_material_params
+ * rebuilds that index. The default upload is not changed by it. */
+#define RTG_PATH_MIS_OFF   0
+#define RTG_PATH_MIS_POWER 1
+int  rtg_path_mis_check(int mode);
+int  rtg_set_path_mis(rtg_handle* h, int mode);
+int  rtg_get_path_mis(rtg_handle* h, int* mode);
+/* The kernels' own weight function on n pairs, on the current device (no handle): w[i] = mis_w(p[i], q[i]). */
+int  rtg_probe_mis_weight(const float* p, const float* q, uint32_t n, float* w);
+/* The solid-angle density the handle's environment mode gives n directions (p_env above; under
+ * RTG_ENV_UNIFORM, or when no table is active, uniformSpherePDF). */
+int  rtg_probe_env_pdf(rtg_handle* h, const float* dirs /* n*3 */, uint32_t n, float* pdf);
+/* The host copy of the triangle -> light map. Before the first RTG_PATH_MIS_POWER setting: RTG_ERR_ARG. */
+int  rtg_light_of_triangle(rtg_handle* h, int32_t* out /* n_triangles */);
 
 /* Add samples [first_sample, first_sample+n_samples) of every pixel in the listed 32x32 tiles
  * (tile id = ty*tilesX + tx, RTBase TILE_SIZE=32; tile_ids=NULL = all tiles) to the film, in
@@ -601,6 +682,7 @@ int  rtg_group_set_env_sampling(rtg_group* g, int mode);  /* rtg_set_env_samplin
 int  rtg_group_set_light_sampling(rtg_group* g, const rtg_light_sampling* p);  /* every rank's handle */
 int  rtg_group_set_material_params(rtg_group* g, const rtg_material_params* params, uint32_t n);  /* every rank's */
 int  rtg_group_set_material_model(rtg_group* g, int mode);  /* rtg_set_material_model on every rank's handle */
+int  rtg_group_set_path_mis(rtg_group* g, int mode);  /* rtg_set_path_mis on every rank's handle */
 int  rtg_group_render(rtg_group* g, uint32_t first_sample, uint32_t n_samples, uint64_t seed);
 int  rtg_group_reduce(rtg_group* g);  /* the films stay per device; the assembled film goes to a separate buffer */
 /* Queued forms (the frame loop of Main.cpp:74-118 on N devices). rtg_group_render_async is every

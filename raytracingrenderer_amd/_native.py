@@ -21,6 +21,7 @@ RTG_ENV_UNIFORM, RTG_ENV_LUMINANCE = 0, 1
 RTG_ENV_MAX_CELLS = 1 << 24
 RTG_LIGHTS_UNIFORM, RTG_LIGHTS_POWER = 0, 1
 RTG_MATERIALS_REFERENCE, RTG_MATERIALS_PHYSICAL = 0, 1
+RTG_PATH_MIS_OFF, RTG_PATH_MIS_POWER = 0, 1
 RTG_MODEL_REFERENCE, RTG_MODEL_CONDUCTOR, RTG_MODEL_PLASTIC, RTG_MODEL_ORENNAYAR = 0, 1, 2, 3
 RTG_ALPHA_DELTA = 0.01
 
@@ -198,6 +199,14 @@ RTG_EXPORTS = [
     ("rtg_group_set_material_params", C.c_int, [C.c_void_p, C.POINTER(rtg_material_params), C.c_uint32]),
     ("rtg_group_set_material_model", C.c_int, [C.c_void_p, C.c_int]),
     ("rtg_probe_material", C.c_int, [f32p, C.c_uint32, f32p]),
+    # path-tracer MIS of emitters (rtg_shade_mis.hip)
+    ("rtg_path_mis_check", C.c_int, [C.c_int]),
+    ("rtg_set_path_mis", C.c_int, [C.c_void_p, C.c_int]),
+    ("rtg_get_path_mis", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    ("rtg_group_set_path_mis", C.c_int, [C.c_void_p, C.c_int]),
+    ("rtg_probe_mis_weight", C.c_int, [f32p, f32p, C.c_uint32, f32p]),
+    ("rtg_probe_env_pdf", C.c_int, [C.c_void_p, f32p, C.c_uint32, f32p]),
+    ("rtg_light_of_triangle", C.c_int, [C.c_void_p, i32p]),
 ]
 
 RTH_EXPORTS = [

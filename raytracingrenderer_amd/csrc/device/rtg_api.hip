@@ -132,6 +132,7 @@ int upload_scene(int device, const HostScene& hs, rtg_handle* h) {
     h->proj = hs.proj;
     h->tri_mat = hs.tri_mat;
     h->n_desc_mats = hs.n_desc_mats;
+    h->light_tri = hs.light_tri;
     h->W = (int)hs.cam.width;
     h->H = (int)hs.cam.height;
     HIPOK(hipMalloc((void**)&h->d_film, (size_t)h->W * h->H * 3 * sizeof(float)));
@@ -200,6 +201,8 @@ void rtg_destroy(rtg_handle* h) {
     (void)hipFree(h->d_light_table);
     (void)hipFree(h->d_phys);
     (void)hipFree(h->d_phys_index);
+    (void)hipFree(h->d_mis_index);
+    (void)hipFree(h->d_mis_ref);
     (void)hipFree(h->d_img);
     (void)hipFree(h->d_nodes); (void)hipFree(h->d_nodesq); (void)hipFree(h->d_leafbox); (void)hipFree(h->d_tris48); (void)hipFree(h->d_shade); (void)hipFree(h->d_mats);
     (void)hipFree(h->d_lights); (void)hipFree(h->d_texinfo); (void)hipFree(h->d_texels); (void)hipFree(h->d_film);

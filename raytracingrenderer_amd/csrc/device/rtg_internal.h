@@ -6,6 +6,7 @@
 #include "rtg_dev.h"
 #include "../../../include/rtg.h"
 #include "rtg_phys.h"
+#include "rtg_mis.h"
 
 #include <hip/hip_runtime.h>
 #include <rocprofiler-sdk-roctx/roctx.h>
@@ -406,6 +407,17 @@ struct rtg_handle {
     PhysMat* d_phys = nullptr;
     unsigned* d_phys_index = nullptr;
     int n_phys = 0;
+    std::vector<unsigned> phys_index;          // d_phys_index's host copy (rtg_set_path_mis's table takes it in)
+    // rtg_set_path_mis (rtg_shade_mis.hip): the per-triangle table of k_shade_mis (MisArgs: the triangle ->
+    // light map from the light list, beside the triangle's parameter record index) and a table of
+    // reference-kind parameter records for renders without the physical model; built by the first
+    // RTG_PATH_MIS_POWER setting, rebuilt when the parameter table is, kept until rtg_destroy
+    int path_mis = RTG_PATH_MIS_OFF;
+    std::vector<int32_t> light_tri;            // rtg_scene_desc.lights (upload_scene; host only)
+    std::vector<int32_t> light_of;             // [triangle] -> light, the map's host copy (rtg_light_of_triangle)
+    uint2* d_mis_index = nullptr;
+    PhysMat* d_mis_ref = nullptr;
+    int n_mis_ref = 0;
 };
 #define RTG_CNT_PENDING 0xFFFFFFFFu
 
@@ -435,6 +447,7 @@ struct HostScene {
     rtg_camera_proj proj{};
     std::vector<uint32_t> tri_mat;  // [triangle] rtg_scene_desc.material, before the merge (the physical
     uint32_t n_desc_mats = 0;       // material model's own index; not uploaded by upload_scene)
+    std::vector<int32_t> light_tri;  // rtg_scene_desc.lights (rtg_set_path_mis's map; not uploaded by upload_scene)
 };
 
 // rtg_bvh.hip: the own binary tree with spatial splits over the triangles (descriptor node format)
@@ -509,6 +522,14 @@ PhysArgs phys_args_of(const rtg_handle* h);
 // one k_shade_phys launch (ALT, TAB; the environment table and the light pick as runtime arguments)
 int launch_shade_phys(bool alt, bool tab, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
                       const PathBufs& p, int b, const EnvTable& env, const LightPick& pick, const PhysArgs& phys);
+// rtg_shade_mis.hip: k_shade_mis's per-triangle table from the light list and the handle's parameter
+// index (a no-op before the first RTG_PATH_MIS_POWER setting); the caller has waited for the device
+int mis_sync_tables(rtg_handle* h);
+// rtg_shade_mis.hip: rtg_set_path_mis is on, the integrator is PATH and the map is built: k_shade_mis
+bool path_mis_active(const rtg_handle* h);
+// one k_shade_mis launch (TAB; the tables as runtime arguments, phys with a null table: the reference model)
+int launch_shade_mis(const rtg_handle* h, bool tab, unsigned grid, hipStream_t st, const ChunkArgs& a, const PathBufs& p,
+                     int b, const EnvTable& env, const LightPick& pick, const PhysArgs& phys);
 // RTG_ERR_ARG (with "who: ..." as the message) for records outside include/rtg.h's ranges
 int material_params_check(const char* who, const rtg_material_params* params, uint32_t n, uint32_t n_materials);
 // rtg_shade.hip: one k_shade launch of `grid` blocks (ALT = alt, TAB = tab) for bounce b

@@ -535,6 +535,25 @@ int rtg_group_set_material_model(rtg_group* g, int mode) {
     return RTG_OK;
 }
 
+int rtg_group_set_path_mis(rtg_group* g, int mode) {
+    if (!g) { g_err = "rtg_group_set_path_mis: null group"; return RTG_ERR_ARG; }
+    // checked once for all ranks, so an argument error leaves every rank's setting as it was
+    if (int rc = rtg_path_mis_check(mode)) return rc;
+    for (rtg_handle* h : g->h) {
+        int prev = RTG_PATH_MIS_OFF;
+        (void)rtg_get_path_mis(h, &prev);
+        const int rc = rtg_set_path_mis(h, mode);
+        if (rc) {
+            for (rtg_handle* u : g->h) {
+                if (u == h) break;
+                (void)rtg_set_path_mis(u, prev);
+            }
+            return rc;
+        }
+    }
+    return RTG_OK;
+}
+
 int rtg_group_render(rtg_group* g, uint32_t first_sample, uint32_t n_samples, uint64_t seed) {
     if (!g) return RTG_ERR_ARG;
     g->reduced = false;

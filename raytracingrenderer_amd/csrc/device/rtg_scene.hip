@@ -516,5 +516,6 @@ int prepare_scene(const rtg_scene_desc* d, HostScene& hs) {
     hs.proj = d->projection;
     hs.tri_mat.assign(d->material, d->material + nt);
     hs.n_desc_mats = d->n_materials;
+    hs.light_tri.assign(d->lights, d->lights + d->n_lights);
     return RTG_OK;
 }

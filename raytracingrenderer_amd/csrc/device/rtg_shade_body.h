@@ -19,6 +19,12 @@
 // NEE evaluates the model in albedo / pi's place; the bounce samples it, and "specular" becomes a
 // property of the sample, not of the material. Without the macro the preprocessor leaves the other
 // kernels the text they had.
+// RTG_SHADE_MIS defined as well (k_shade_mis, rtg_shade_mis.hip; the including kernel also sets the
+// MisArgs mis, and ALT = false): rtg_set_path_mis's estimator. The NEE term is weighted against the BSDF's
+// density of the shadow ray's direction, the BSDF sample's density travels in thr.w, and an emitter hit
+// or a miss after a non-specular sample is weighted against NEE's density of it (the hit triangle's
+// light comes from a map indexed by the triangle id, loaded beside the shading record). Every statement
+// of it stands inside #ifdef RTG_SHADE_MIS.
     __shared__ unsigned s_cnt[2][RTG_TB / 64];
     __shared__ unsigned s_base[2];
     __shared__ float4 s_sho[RTG_TB], s_shd[RTG_TB];  // NEE ray staged until its queue position is known
@@ -89,6 +95,9 @@
 #ifdef RTG_SHADE_PHYS
         unsigned pmi = 0;  // the hit triangle's parameter record
 #endif
+#ifdef RTG_SHADE_MIS
+        int lof = -1;  // the hit triangle's light (-1: it is not in the light list)
+#endif
         if (valid) {
             unsigned j = i;  // bounce 0: the pixel's camera ray and first hit (k_generate), shared by its samples
             if (lean0 && !a.cam_mode) {  // (per-sample camera rays, k_generate_sampled: the path's own)
@@ -99,7 +108,13 @@
             rd = in_d[j];
             h = p.hits[j];
             if (h.x < RTG_FLT_MAX) S = s.shade[__float_as_int(h.y)];
-#ifdef RTG_SHADE_PHYS
+#ifdef RTG_SHADE_MIS
+            if (h.x < RTG_FLT_MAX) {  // one 8-byte load: the parameter record and the light of the triangle
+                const uint2 ix = mis.index[1 + __float_as_int(h.y)];
+                pmi = ix.x;
+                lof = (int)ix.y;
+            }
+#elif defined(RTG_SHADE_PHYS)
             if (h.x < RTG_FLT_MAX) pmi = pm.index[__float_as_int(h.y)];
 #endif
         }
@@ -129,6 +144,9 @@
             v3 env_dir = d, x = o, sn = d, alb = d, l_p2 = o, l_em = d;
             float l_g = 0.0f, l_pdf = 0.0f;
             float l_pp = 0.0f;  // PICK: the picked light's pmf * l_pdf (one value across the lookup, not two)
+#ifdef RTG_SHADE_MIS
+            float l_pl = 0.0f;  // the light sample's density with respect to solid angle at x
+#endif
 #ifdef RTG_SHADE_PHYS
             int ptag = RTG_MODEL_REFERENCE;  // the hit's model tag (stage 1)
 #endif
@@ -180,8 +198,24 @@
                 if (ALT && a.mode == RTG_INTEGRATOR_NORMALS) {  // viewNormals (Renderer.h:572-582)
                     c = mk(fabsf(sn.x), fabsf(sn.y), fabsf(sn.z));
                 } else if (M.is_light) {
+#ifdef RTG_SHADE_MIS
+                    // thr * emission; after a non-specular sample weighted against NEE's density of this
+                    // point (an emitter outside the light list: no NEE sample reaches it, weight 1)
+                    c = mul(thr, mk(M.emission.x, M.emission.y, M.emission.z));
+                    if (!can_hit && lof >= 0) {
+                        const DevLight& HL = TAB ? s_lt[lof] : s.lights[lof];
+                        const float cos_h = wmax(-dot(d, mk(HL.gn.x, HL.gn.y, HL.gn.z)), 0.0f);
+                        if (cos_h > 0.0f) {
+                            const float pmf_h = PICK ? __uint_as_float((TAB ? s_pk : lpk.table)[lof].z) : s.pmf;
+                            c = muls(c, mis_w(thr4.w, pdf_area_to_solid(pmf_h * HL.v2.w, t * t, cos_h)));
+                        } else {
+                            c = mk(0.0f, 0.0f, 0.0f);  // the back side: NEE cannot reach it either
+                        }
+                    }
+#else
                     c = (ALT && a.mode != RTG_INTEGRATOR_PATH) ? mk(M.emission.x, M.emission.y, M.emission.z)  // emit()
                         : can_hit ? mul(thr, mk(M.emission.x, M.emission.y, M.emission.z)) : mk(0.0f, 0.0f, 0.0f);
+#endif
                 } else if (ALT && a.mode == RTG_INTEGRATOR_ALBEDO) {  // BSDF::evaluate(sd, (0,1,0))
                     const v3 alb = tex_sample(s, M, tu, tv);
                     c = M.kind == RTG_MAT_MIRROR ? alb : (M.kind == RTG_MAT_GLASS ? mk(0.0f, 0.0f, 0.0f) : divs_pi(alb));
@@ -324,6 +358,10 @@
                             const float l2 = length_sq(wi);
                             wi = normalize(wi);
                             l_g = (wmax(dot(wi, sn), 0.0f) * wmax(-dot(wi, mk(L.gn.x, L.gn.y, L.gn.z)), 0.0f)) / l2;
+#ifdef RTG_SHADE_MIS
+                            l_pl = pdf_area_to_solid((PICK ? pmf : s.pmf) * l_pdf, l2,
+                                                     wmax(-dot(wi, mk(L.gn.x, L.gn.y, L.gn.z)), 0.0f));
+#endif
                         } else {  // EnvironmentMap::sample: uniformSampleSphere(next(), next())
                             v3 wi;
                             bool ok = true;
@@ -344,6 +382,9 @@
                             env_dir = wi;  // its radiance: EnvironmentMap::evaluate(wi), below (used iff g > 0)
                             env_need = l_g > 0;
                             env_light = true;
+#ifdef RTG_SHADE_MIS
+                            l_pl = (PICK ? pmf : s.pmf) * l_pdf;
+#endif
                         }
                         if (PICK) l_pp = pmf * l_pdf;
                     }
@@ -354,7 +395,24 @@
             // sample's radiance are the same EnvironmentMap::evaluate (Lights.h:150-157), so a wave
             // holding both kinds of lane runs it once instead of in two divergent branches.
             const v3 E = env_need ? env_eval(s, env_dir) : mk(0.0f, 0.0f, 0.0f);
+#ifdef RTG_SHADE_MIS
+            if (miss) {
+                // bounce 0: E. Later: thr * E, after a non-specular sample weighted against NEE's density of
+                // the direction when the environment is in the light list (not Renderer.h:390's unweighted E)
+                c = E;
+                if (!lean0) {
+                    c = mul(thr, E);
+                    const int env_li = can_hit ? -1 : (int)mis.index[0].y;
+                    if (env_li >= 0) {
+                        const float pmf_e = PICK ? __uint_as_float((TAB ? s_pk : lpk.table)[env_li].z) : s.pmf;
+                        const float p_e = ENV ? env_pdf_luminance(et, d) : uniform_sphere_pdf();
+                        c = muls(c, mis_w(thr4.w, pmf_e * p_e));
+                    }
+                }
+            }
+#else
             if (miss) c = E;
+#endif
             if (stage == 1) {
                 const DevMat& M = TAB ? s_mat[mid] : s.mats[mid];
                 const v3 wo = neg(d);
@@ -381,6 +439,13 @@
                     const v3 f = divs_pi(alb);  // BSDF::evaluate
 #endif
                     ld = divs(muls(mul(f, emitted), l_g), PICK ? l_pp : pmf * l_pdf);
+#ifdef RTG_SHADE_MIS
+                    {  // weighted against the BSDF's density of the shadow ray's direction
+                        const float p_b = ptag != RTG_MODEL_REFERENCE ? phys_pdf(Q, to_local(fr, wo), to_local(fr, sd))
+                                                                      : bsdf_pdf_lambert(fr, sd);
+                        ld = muls(ld, mis_w(l_pl, p_b));
+                    }
+#endif
                     const v3 cvis = mul(thr, ld);
                     s_sho[threadIdx.x] = make_float4(so.x, so.y, so.z, maxt);
                     // Visible is the common case: contrib takes thr * Ld now and k_trace
@@ -413,6 +478,11 @@
                             live = pdf > 0.0f;
                         } else {
                             wi = bsdf_sample(M.kind, M.int_ior, M.ext_ior, alb, fr, wo, smp, ind, pdf);
+#ifdef RTG_SHADE_MIS
+                            // a cosine sample on the horizon (pdf 0): the path ends here, as the material model's
+                            // guard ends it, where PATH carries 0 / 0 on (a miss would show it: thr * E)
+                            live = pdf > 0.0f;
+#endif
                         }
                         st = smp.s;
                         if (live) {
@@ -422,7 +492,11 @@
                             n_o = make_float4(no.x, no.y, no.z, __int_as_float(pid));
                             n_d = make_float4(wi.x, wi.y, wi.z, sp ? 1.0f : 0.0f);  // canHitLight
                             want_ext = true;
+#ifdef RTG_SHADE_MIS
+                            n_t = make_float4(thr.x, thr.y, thr.z, sp ? 0.0f : pdf);  // .w: the sample's density
+#else
                             n_t = make_float4(thr.x, thr.y, thr.z, 0.0f);
+#endif
                             n_r = st;
                             nterms = (b + 1) | ((sp ? 1 : 0) << 8);
                         }

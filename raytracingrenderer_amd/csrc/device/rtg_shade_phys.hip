@@ -142,7 +142,8 @@ static int build_phys_table(rtg_handle* h) {
     h->n_phys = (int)uniq.size();
     h->phys_any = any;
     h->phys_built = true;
-    return RTG_OK;
+    h->phys_index.swap(index);
+    return mis_sync_tables(h);  // (rtg_set_path_mis's table holds a copy of the index)
 }
 
 extern "C" {

@@ -35,6 +35,9 @@
 // and Oren-Nayar materials shade as the reference's Lambertian stubs; physical: GGX conductor, coated
 // plastic and Oren-Nayar from the scene's own roughness, eta, k, IORs and alpha), for one device and for
 // -gpus / -devices alike.
+// Path-tracer MIS (rtg_set_path_mis): -pathMIS off|power (off: the reference's pathTrace; power: NEE and
+// BSDF-sampled emitter hits combined with the power heuristic, a miss weighted by the throughput), for one
+// device and for -gpus / -devices alike.
 // Multi-GPU (one node): -gpus N renders on devices 0..N-1, -devices a,b,... on a list. Rank r
 // renders the 32x32 tiles with (tile_x + tile_y) % N == r, and the film is assembled on the first
 // device from every device's own tiles (packed, one RCCL send per device, scattered) before it is
@@ -122,6 +125,9 @@ int main(int argc, char** argv) {
     const std::string mtl = get("-materials", "reference");
     if (mtl != "reference" && mtl != "physical") return die("-materials", "one of reference, physical");
     const bool physical = mtl == "physical";
+    const std::string pmn = get("-pathMIS", "off");
+    if (pmn != "off" && pmn != "power") return die("-pathMIS", "one of off, power");
+    const int path_mis = pmn == "power" ? RTG_PATH_MIS_POWER : RTG_PATH_MIS_OFF;
     uint32_t n_params = 0;
     const rtg_material_params* params = rth_scene_material_params(scene, &n_params);
     rtg_handle* rt = nullptr;
@@ -135,6 +141,7 @@ int main(int argc, char** argv) {
         if (physical && (rtg_set_material_params(rt, params, n_params) != 0 ||
                          rtg_set_material_model(rt, RTG_MATERIALS_PHYSICAL) != 0))
             return die("rtg_set_material_model", rtg_last_error());
+        if (rtg_set_path_mis(rt, path_mis) != 0) return die("rtg_set_path_mis", rtg_last_error());
     } else {
         if (rtg_group_create(devices.data(), (int)devices.size(), rth_scene_desc(scene), &grp) != 0)
             return die("rtg_group_create", rtg_last_error());
@@ -145,6 +152,7 @@ int main(int argc, char** argv) {
         if (physical && (rtg_group_set_material_params(grp, params, n_params) != 0 ||
                          rtg_group_set_material_model(grp, RTG_MATERIALS_PHYSICAL) != 0))
             return die("rtg_group_set_material_model", rtg_last_error());
+        if (rtg_group_set_path_mis(grp, path_mis) != 0) return die("rtg_group_set_path_mis", rtg_last_error());
         std::printf("%d devices, own-tile film exchange by %s\n", (int)devices.size(),
                     rtg_group_uses_rccl(grp) ? "RCCL (ncclSend/ncclRecv)"
                     : devices.size() == 1    ? "none (one device)"

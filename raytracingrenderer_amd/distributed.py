@@ -137,7 +137,7 @@ def reduce_film(film_tensor, dist, dst=0):
 
 
 def render_sharded(rt, n_samples, rank, world, dist=None, film_tensor=None, first_sample=0, exchange=None,
-                   camera_sampling=None, material_model=None):
+                   camera_sampling=None, material_model=None, path_mis=None):
     """Render this rank's tiles with RayTracer `rt`, then assemble the film on rank 0.
 
     camera_sampling: a dict of RayTracer.set_camera_sampling's arguments (e.g. {"filter": "tent"}),
@@ -146,6 +146,7 @@ def render_sharded(rt, n_samples, rank, world, dist=None, film_tensor=None, firs
     None leaves the tracer's setting as it is.
     material_model: "reference" or "physical" (RayTracer.set_material_model), applied likewise; every
     rank must pass the same one. None leaves the tracer's setting as it is.
+    path_mis: "off" or "power" (RayTracer.set_path_mis), applied likewise.
 
     world > 1: rank 0's film_tensor (torch float32 HxWx3) receives the whole film from every rank's
     own tiles (FilmExchange; pass `exchange` to reuse its buffers across calls); a CUDA tensor is
@@ -158,6 +159,8 @@ def render_sharded(rt, n_samples, rank, world, dist=None, film_tensor=None, firs
         rt.set_camera_sampling(**camera_sampling)
     if material_model is not None:
         rt.set_material_model(material_model)
+    if path_mis is not None:
+        rt.set_path_mis(path_mis)
     rt.render(n_samples, tiles=tiles, first_sample=first_sample)
     if film_tensor is None:
         if world > 1:

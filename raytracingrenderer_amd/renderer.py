@@ -261,6 +261,39 @@ def _material_model(mode):
     return int(mode)
 
 
+PATH_MIS = {"off": N.RTG_PATH_MIS_OFF, "power": N.RTG_PATH_MIS_POWER}
+
+
+def _path_mis(mode):
+    """The RTG_PATH_MIS_* value of set_path_mis's argument (a name of PATH_MIS or a value; an unknown
+    value is the library's error)."""
+    if isinstance(mode, str):
+        if mode not in PATH_MIS:
+            raise ValueError("unknown path MIS mode %r (one of %s)" % (mode, ", ".join(PATH_MIS)))
+        return PATH_MIS[mode]
+    return int(mode)
+
+
+def path_mis_check(mode):
+    """rtg_set_path_mis's argument check alone (rtg_path_mis_check; no GPU): raises NativeError for an
+    unknown mode."""
+    lib = N.rtg()
+    _check(lib.rtg_path_mis_check(_path_mis(mode)), lib.rtg_last_error)
+
+
+def mis_weight_probe(p, q):
+    """The path-tracer MIS kernels' own weight function (rtg_probe_mis_weight, test surface) on the
+    current device: mis_w(p[i], q[i]) for p, q (n,) float32."""
+    p, q = (np.ascontiguousarray(v, np.float32).reshape(-1) for v in (p, q))
+    if len(p) != len(q):
+        raise ValueError("mis_weight_probe: p and q must have one length")
+    w = np.zeros(len(p), np.float32)
+    lib = N.rtg()
+    _check(lib.rtg_probe_mis_weight(N.ptr(p, C.c_float), N.ptr(q, C.c_float), len(p), N.ptr(w, C.c_float)),
+           lib.rtg_last_error)
+    return w
+
+
 def _material_params_array(params):
     """A ctypes array of rtg_material_params from a sequence of them."""
     params = list(params)
@@ -473,6 +506,42 @@ class RayTracer:
         return {v: k for k, v in MATERIAL_MODELS.items()}.get(m.value, m.value)
 
     material_probe = staticmethod(material_probe)
+
+    def set_path_mis(self, mode="off"):
+        """Multiple importance sampling of emitters in the path tracer (rtg_set_path_mis). "off"
+        (default): pathTrace as the reference has it, NEE alone after a non-specular bounce and the
+        background unweighted on a miss, the reference's films bit for bit. "power": the NEE sample and the
+        BSDF sample of every non-specular vertex are combined with the power heuristic, and a miss is
+        weighted by the path throughput (include/rtg.h has the definition): the same paths as "off" for
+        the same seed, other weights; the correct estimator under an environment light, where "off"
+        counts the environment twice. Applies to render(), adaptiveRender() and the "path" integrator
+        only, with every environment, light selection, material and camera setting; not to "direct",
+        "direct_mis", "albedo", "normals", lightTracer(), instantRadiosity() or the denoiser's guides."""
+        _check(self._lib.rtg_set_path_mis(self._h, _path_mis(mode)), self._lib.rtg_last_error)
+
+    def path_mis(self):
+        """The current setting, "off" or "power"."""
+        m = C.c_int()
+        _check(self._lib.rtg_get_path_mis(self._h, C.byref(m)), self._lib.rtg_last_error)
+        return {v: k for k, v in PATH_MIS.items()}.get(m.value, m.value)
+
+    mis_weight_probe = staticmethod(mis_weight_probe)
+
+    def env_pdf(self, dirs):
+        """The solid-angle density the current environment mode gives directions (n, 3)
+        (rtg_probe_env_pdf): the luminance table's cell density over sin theta, or 1 / (4 pi)."""
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        out = np.zeros(len(d), np.float32)
+        _check(self._lib.rtg_probe_env_pdf(self._h, N.ptr(d, C.c_float), len(d), N.ptr(out, C.c_float)),
+               self._lib.rtg_last_error)
+        return out
+
+    def light_of_triangle(self):
+        """The triangle -> light map of set_path_mis("power") (rtg_light_of_triangle): (n_triangles,)
+        int32, the triangle's index in Scene.lights or -1."""
+        out = np.zeros(self.scene.desc.n_tris, np.int32)
+        _check(self._lib.rtg_light_of_triangle(self._h, N.ptr(out, C.c_int32)), self._lib.rtg_last_error)
+        return out
 
     def light_records(self):
         """The light records as uploaded (rtg_light_records): (n_lights, 20) float32 = v0.xyz area |
@@ -714,6 +783,10 @@ class RayTracerGroup:
         """RayTracer.set_light_sampling on every rank (rtg_group_set_light_sampling)."""
         p = _light_sampling(mode, uniform_share)
         _check(self._lib.rtg_group_set_light_sampling(self._g, C.byref(p)), self._lib.rtg_last_error)
+
+    def set_path_mis(self, mode="off"):
+        """RayTracer.set_path_mis on every rank (rtg_group_set_path_mis)."""
+        _check(self._lib.rtg_group_set_path_mis(self._g, _path_mis(mode)), self._lib.rtg_last_error)
 
     def set_material_model(self, mode="reference"):
         """RayTracer.set_material_model on every rank (rtg_group_set_material_params / _model)."""

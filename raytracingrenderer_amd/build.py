@@ -243,6 +243,12 @@ def build_sbvh_check(force=False):
     return _build_test_program("sbvh_check", [os.path.join(CSRC, "device", "rtg_bvh.hip")], ["rth"], force)
 
 
+def build_walk_model(force=False):
+    """rtg_bvh.hip's host code + librth: a CPU model of the 4-wide walk's fetch counts on the own tree,
+    as built and after optimise_bvh2; tests/test_bvh_opt.py runs it."""
+    return _build_test_program("walk_model", [os.path.join(CSRC, "device", "rtg_bvh.hip")], ["rth"], force)
+
+
 def build_scene_digest(force=False):
     """librtg's prepare_scene on a loaded scene, one digest per device record array;
     tests/test_scene_digest.py runs it."""

@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <array>
 #include <atomic>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <thread>
@@ -333,6 +334,231 @@ struct Builder {
     }
 };
 
+// Insertion-based optimisation of the finished tree (Bittner, Hapala, Havran 2013): in passes, the
+// internal nodes that cost the most for what they hold are taken out with their parent, and their two
+// children are put back where they add the least surface area to the tree (the new parent's box plus
+// what the ancestors' boxes grow by), found by a branch-and-bound search from the root. Leaves move as
+// they are: a reference keeps its triangle and its fragment box, so the slots' coverage of the
+// triangles (the exactness argument above) is untouched; only the internal topology changes.
+//
+// A region is a subtree down to its leaves or to nodes marked `stop` (whole subtrees that move as
+// units). Regions that share no node can be optimised on different threads: all state is per node.
+struct Optimiser {
+    std::vector<int32_t>& L;     // links, ids of the stitched tree
+    const std::vector<Ref>& R;   // the leaves' references
+    std::vector<int> parent, height;  // height: levels below the node (a leaf: 0)
+    std::vector<Box> box;
+    std::vector<double> area;
+    std::vector<char> stop;
+
+    Optimiser(std::vector<int32_t>& l, const std::vector<Ref>& r)
+        : L(l), R(r), parent(r.size(), -1), height(r.size(), 0), box(r.size()), area(r.size(), 0.0), stop(r.size(), 0) {}
+
+    bool leaf(int n) const { return L[(size_t)n * 4] < 0 || stop[n]; }
+    int& child(int n, int k) { return L[(size_t)n * 4 + k]; }
+
+    void refit_one(int n) {
+        const int a = child(n, 0), b = child(n, 1);
+        box[n] = box[a];
+        box[n].add(box[b]);
+        area[n] = box[n].area();
+        height[n] = 1 + std::max(height[a], height[b]);
+    }
+    void refit_up(int n) {
+        for (; n >= 0; n = parent[n]) refit_one(n);
+    }
+    void replace_child(int g, int from, int to, int& root) {
+        parent[to] = g;
+        if (g < 0) { root = to; return; }
+        child(g, child(g, 0) == from ? 0 : 1) = to;
+    }
+    // take x and its parent out: x's sibling takes the parent's place. Returns the freed parent.
+    int unlink(int x, int& root) {
+        const int f = parent[x];
+        const int y = child(f, 0) == x ? child(f, 1) : child(f, 0);
+        const int g = parent[f];
+        replace_child(g, f, y, root);
+        refit_up(g);
+        return f;
+    }
+    // the free node f takes y's place, with the children y and x
+    void link(int x, int y, int f, int& root) {
+        replace_child(parent[y], y, f, root);
+        child(f, 0) = y;
+        child(f, 1) = x;
+        parent[y] = parent[x] = f;
+        refit_up(f);
+    }
+
+    struct Cand {
+        double cost;  // the ancestors' growth: a lower bound of every position below, less x's own area
+        int node, depth;
+        bool operator<(const Cand& o) const { return cost > o.cost || (cost == o.cost && node > o.node); }
+    };
+    // where the detached subtree x adds the least area, among the positions that keep every path of
+    // the region within `limit` levels; -1 when there is none
+    int best_position(int x, int root, int limit, std::vector<Cand>& heap) const {
+        const Box& bx = box[x];
+        const double ax = area[x];
+        double best_cost = INFINITY;
+        int best = -1;
+        heap.clear();
+        heap.push_back(Cand{0.0, root, 0});
+        while (!heap.empty()) {
+            std::pop_heap(heap.begin(), heap.end());
+            const Cand c = heap.back();
+            heap.pop_back();
+            if (c.cost + ax >= best_cost) break;
+            Box u = box[c.node];
+            u.add(bx);
+            const double total = c.cost + u.area();
+            if (total < best_cost && c.depth + 1 + std::max(height[c.node], height[x]) <= limit) {
+                best_cost = total;
+                best = c.node;
+            }
+            const double below = total - area[c.node];
+            if (!leaf(c.node) && below + ax < best_cost)
+                for (int k = 0; k < 2; ++k) {
+                    heap.push_back(Cand{below, L[(size_t)c.node * 4 + k], c.depth + 1});
+                    std::push_heap(heap.begin(), heap.end());
+                }
+        }
+        return best;
+    }
+
+    // node n (internal, not the root) and its parent leave the tree; n's children are put back, the
+    // larger first. If the second finds no position within the depth limit, the old shape is restored.
+    void reinsert_children(int n, int& root, int limit, std::vector<Cand>& heap) {
+        int a = child(n, 0), b = child(n, 1);
+        if (area[a] < area[b]) std::swap(a, b);
+        const int s = child(parent[n], 0) == n ? child(parent[n], 1) : child(parent[n], 0);
+        const int f1 = unlink(a, root);  // = n
+        const int f2 = unlink(b, root);  // = n's parent
+        const int pa = best_position(a, root, limit, heap);
+        if (pa >= 0) {
+            link(a, pa, f1, root);
+            const int pb = best_position(b, root, limit, heap);
+            if (pb >= 0) { link(b, pb, f2, root); return; }
+            unlink(a, root);
+        }
+        child(f1, 0) = a;
+        child(f1, 1) = b;
+        parent[a] = parent[b] = f1;
+        refit_one(f1);
+        link(f1, s, f2, root);
+    }
+
+    // Optimises the region below `root`; returns its root afterwards (another node may have become it).
+    int region(int root, int limit, const SbvhOpt& o) {
+        std::vector<int> nodes, st{root};
+        while (!st.empty()) {  // pre-order: children after their parents
+            const int n = st.back();
+            st.pop_back();
+            nodes.push_back(n);
+            if (leaf(n)) continue;
+            for (int k = 0; k < 2; ++k) { parent[child(n, k)] = n; st.push_back(child(n, k)); }
+        }
+        parent[root] = -1;
+        for (size_t i = nodes.size(); i-- > 0;) {
+            const int n = nodes[i];
+            if (stop[n]) continue;  // a region of its own, optimised before: box and height are set
+            if (L[(size_t)n * 4] >= 0) { refit_one(n); continue; }
+            box[n] = Box();
+            box[n].add(R[n]);
+            area[n] = box[n].area();
+            height[n] = 0;
+        }
+        std::vector<std::pair<double, int>> rank;
+        std::vector<Cand> heap;
+        auto area_sum = [&] {
+            double s = 0.0;
+            for (int n : nodes)
+                if (!leaf(n)) s += area[n];
+            return s;
+        };
+        double before = area_sum();
+        for (int pass = 0; pass < o.passes; ++pass) {
+            rank.clear();
+            for (int n : nodes) {
+                if (leaf(n) || n == root) continue;
+                const double a = area[n], c0 = area[child(n, 0)], c1 = area[child(n, 1)];
+                double m = a;
+                if (o.priority == 0) {
+                    const double mean = 0.5 * (c0 + c1), mn = std::min(c0, c1);
+                    m = mean > 0.0 && mn > 0.0 ? a * (a / mean) * (a / mn) : (a > 0.0 ? INFINITY : 0.0);
+                }
+                rank.emplace_back(m, n);
+            }
+            if (rank.empty()) break;
+            std::sort(rank.begin(), rank.end(), [](const std::pair<double, int>& x, const std::pair<double, int>& y) {
+                return x.first > y.first || (x.first == y.first && x.second < y.second);
+            });
+            const size_t take = std::min(rank.size(), std::max<size_t>(1, (size_t)((double)rank.size() * o.frac)));
+            for (size_t i = 0; i < take; ++i) {
+                const int n = rank[i].second;
+                if (n != root) reinsert_children(n, root, limit, heap);  // (an internal node stays one)
+            }
+            const double after = area_sum();
+            const bool done = before - after < o.stop * before;
+            before = after;
+            if (done) break;
+        }
+        return root;
+    }
+};
+
+// optimise_bvh2: the deferred subtrees (their roots `sub_roots`) each on its own, on the thread pool,
+// then the levels above them serially with those subtrees as units; without deferred subtrees the
+// whole tree serially. Every region is optimised sequentially, so the result does not depend on the
+// thread count or timing. Then the nodes are renumbered in pre-order (node 0 the root, children after
+// their parents). A region's paths stay within 100 levels, the whole tree's within 120, unless the
+// builder's own were longer.
+void optimise_bvh2(std::vector<int32_t>& L, std::vector<Ref>& R, const std::vector<int>& sub_roots, size_t n_top,
+                   int threads, const SbvhOpt& o) {
+    Optimiser op(L, R);
+    std::vector<int> new_root(sub_roots.size());
+    {
+        std::atomic<size_t> next{0};
+        std::vector<std::thread> pool;
+        for (int t = 0; t < std::min<int>(threads, (int)sub_roots.size()); ++t)
+            pool.emplace_back([&]() {
+                for (size_t k; (k = next.fetch_add(1)) < sub_roots.size();) new_root[k] = op.region(sub_roots[k], 100, o);
+            });
+        for (auto& t : pool) t.join();
+    }
+    if (!sub_roots.empty()) {  // the top levels' links to the subtrees' roots
+        std::vector<int> moved(R.size(), -1);
+        for (size_t k = 0; k < sub_roots.size(); ++k) {
+            moved[sub_roots[k]] = new_root[k];
+            op.stop[new_root[k]] = 1;
+        }
+        // (the first n_top nodes are the top levels' and the placeholders: the links to patch are theirs)
+        for (size_t i = 0; i < n_top; ++i)
+            if (L[i * 4] >= 0 && moved[i] < 0)
+                for (int k = 0; k < 2; ++k)
+                    if (moved[L[i * 4 + k]] >= 0) L[i * 4 + k] = moved[L[i * 4 + k]];
+    }
+    const int root = op.region(0, 120, o);
+    std::vector<int32_t> L2;
+    std::vector<Ref> R2;
+    L2.reserve(L.size());
+    R2.reserve(R.size());
+    std::vector<std::pair<int, int>> st{{root, -1}};  // node, the slot of its parent's link to it
+    while (!st.empty()) {
+        const auto [n, slot] = st.back();
+        st.pop_back();
+        const int id = (int)R2.size();
+        if (slot >= 0) L2[slot] = id;
+        L2.insert(L2.end(), &L[(size_t)n * 4], &L[(size_t)n * 4] + 4);
+        R2.push_back(R[n]);
+        if (L[(size_t)n * 4] < 0) continue;
+        st.push_back({L[(size_t)n * 4 + 1], id * 4 + 1});
+        st.push_back({L[(size_t)n * 4], id * 4});
+    }
+    L.swap(L2);
+    R.swap(R2);
+}
+
 }  // namespace
 
 // The own binary tree with spatial splits over the scene's triangles (rtg_scene.hip's prepare_scene
@@ -342,6 +568,11 @@ struct Builder {
 // and stitched in (a subtree's root takes its placeholder's id; children keep larger ids than their
 // parents). false: non-finite input or a degenerate tree (the caller then keeps another tree).
 bool build_sbvh(const rtg_scene_desc* d, std::vector<int32_t>& lk, std::vector<float>& bd) {
+    SbvhOpt opt;
+    return build_sbvh_opt(d, lk, bd, opt);
+}
+
+bool build_sbvh_opt(const rtg_scene_desc* d, std::vector<int32_t>& lk, std::vector<float>& bd, SbvhOpt& opt) {
     const uint32_t nt = d->n_tris;
     if (nt < 2) return false;
     for (size_t k = 0; k < (size_t)nt * 9; ++k)
@@ -365,7 +596,7 @@ bool build_sbvh(const rtg_scene_desc* d, std::vector<int32_t>& lk, std::vector<f
     Builder top(d);
     top.root_area = root.area();
     top.budget = (long)((double)nt * RTG_SBVH_DUP);
-    top.stop_depth = nt < 50000 || threads == 1 ? (1 << 30) : 6;  // 2^6 = 64 subtrees at most
+    top.stop_depth = nt < 50000 ? (1 << 30) : 6;  // 2^6 = 64 subtrees at most, whatever the thread count
     top.build(refs, 0);
     if (!top.ok) return false;
     // the sub-builds: references as deferred, budget split by reference count
@@ -391,6 +622,7 @@ bool build_sbvh(const rtg_scene_desc* d, std::vector<int32_t>& lk, std::vector<f
     for (const Builder& b : sub)
         if (!b.ok) return false;
     // stitch: the top nodes, then each sub-build's nodes 1.. after them; its node 0 is the placeholder
+    const size_t n_top = top.leaf_ref.size();
     std::vector<int32_t> L = std::move(top.lk);
     std::vector<Ref> R = std::move(top.leaf_ref);
     for (size_t k = 0; k < nsub; ++k) {
@@ -409,6 +641,13 @@ bool build_sbvh(const rtg_scene_desc* d, std::vector<int32_t>& lk, std::vector<f
                 R.push_back(b.leaf_ref[j]);
             }
         }
+    }
+    if (opt.passes > 0 && nt >= opt.min_tris) {
+        std::vector<int> sub_roots;
+        for (auto& dr : top.deferred) sub_roots.push_back(dr.first);
+        const auto t0 = std::chrono::steady_clock::now();
+        optimise_bvh2(L, R, sub_roots, n_top, threads, opt);
+        opt.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     // bounds bottom-up (children have larger ids): a leaf's fragment box rounded outward to float and
     // inflated by eta; an internal node's the float union of its children's

@@ -94,6 +94,24 @@ using namespace rtgd;
 #ifndef RTG_SBVH_DUP
 #define RTG_SBVH_DUP 0.5    // at most this many extra references per triangle in all
 #endif
+// Insertion-based optimisation of that tree after the build (Bittner, Hapala, Havran 2013; rtg_bvh.hip
+// optimise_bvh2)
+#ifndef RTG_BVH_OPT_PASSES
+#define RTG_BVH_OPT_PASSES 20    // passes at most (0: the tree stays as built)
+#endif
+#ifndef RTG_BVH_OPT_FRAC
+#define RTG_BVH_OPT_FRAC 1.0     // share of the internal nodes a pass detaches and reinserts
+#endif
+#ifndef RTG_BVH_OPT_PRIORITY
+#define RTG_BVH_OPT_PRIORITY 0   // what ranks them: 0 Bittner's area * area/mean child * area/min child, 1 area
+#endif
+#ifndef RTG_BVH_OPT_STOP
+#define RTG_BVH_OPT_STOP 1e-5    // a pass that lowers the area sum by less than this fraction is the last
+#endif
+#ifndef RTG_BVH_OPT_MIN_TRIS
+#define RTG_BVH_OPT_MIN_TRIS 50000  // scenes below this many triangles (the ones build_sbvh builds without
+#endif                              // deferred subtrees) keep the tree as built: their device records are
+                                    // pinned (tests/test_scene_digest.py)
 // RTG_DEBUG=1 (a diagnostic build only) compiles k_trace's per-wave clocks (RTG_OPT_WAVETIME) and
 // the fetch capture + replay of the locality-matched roofline (RTG_OPT_CAPTURE, rtg_debug_replay).
 #define RTG_CAP_LEN 64
@@ -452,6 +470,41 @@ struct HostScene {
 
 // rtg_bvh.hip: the own binary tree with spatial splits over the triangles (descriptor node format)
 bool build_sbvh(const rtg_scene_desc* d, std::vector<int32_t>& lk, std::vector<float>& bd);
+// ... with the post-build optimisation's settings given (build_sbvh passes the RTG_BVH_OPT_* constants;
+// tests/native/walk_model.cpp compares settings). ms: the time the optimisation took.
+struct SbvhOpt {
+    int passes = RTG_BVH_OPT_PASSES;
+    double frac = RTG_BVH_OPT_FRAC;
+    int priority = RTG_BVH_OPT_PRIORITY;
+    double stop = RTG_BVH_OPT_STOP;
+    uint32_t min_tris = RTG_BVH_OPT_MIN_TRIS;
+    double ms = 0.0;
+};
+bool build_sbvh_opt(const rtg_scene_desc* d, std::vector<int32_t>& lk, std::vector<float>& bd, SbvhOpt& opt);
+// The slots of the wide node made from binary node n2 (links lk, bounds bd in the descriptor's node
+// format): a cut of the subtree below it, grown by repeatedly opening the internal slot of largest
+// surface area (the first of equals; leaves stay slots). Returns their count, 2 to 4.
+static inline int wide_cut(const int32_t* lk, const float* bd, int n2, int slots[4]) {
+    auto internal = [&](int i) { return lk[(size_t)i * 4] >= 0; };
+    auto area = [&](int i) {
+        const float* b = bd + (size_t)i * 6;
+        const double x = b[3] - b[0], y = b[4] - b[1], z = b[5] - b[2];
+        return x * y + y * z + z * x;
+    };
+    int n = 2;
+    slots[0] = lk[(size_t)n2 * 4];
+    slots[1] = lk[(size_t)n2 * 4 + 1];
+    while (n < 4) {
+        int best_k = -1;
+        for (int k = 0; k < n; ++k)
+            if (internal(slots[k]) && (best_k < 0 || area(slots[k]) > area(slots[best_k]))) best_k = k;
+        if (best_k < 0) break;
+        const int c = slots[best_k];
+        slots[best_k] = lk[(size_t)c * 4];
+        slots[n++] = lk[(size_t)c * 4 + 1];
+    }
+    return n;
+}
 // rtg_scene.hip
 int prepare_scene(const rtg_scene_desc* d, HostScene& hs);
 // rtg_api.hip

@@ -342,25 +342,11 @@ int prepare_scene(const rtg_scene_desc* d, HostScene& hs) {
         };
         hs.rebuilt = rebuilt;
         auto internal = [&](int i) { return LK[(size_t)i * 4] >= 0; };
-        auto area = [&](int i) {
-            const float* b = BD + (size_t)i * 6;
-            const double x = b[3] - b[0], y = b[4] - b[1], z = b[5] - b[2];
-            return x * y + y * z + z * x;
-        };
-        // the slots of the wide node made from BVH2 node n2: a cut of its subtree below it
+        // the slots of the wide node made from BVH2 node n2: a cut of its subtree below it (wide_cut)
         auto cut = [&](int n2) {
-            std::vector<int> slots;
-            slots = {LK[(size_t)n2 * 4], LK[(size_t)n2 * 4 + 1]};
-            while ((int)slots.size() < 4) {
-                int best_k = -1;
-                for (int k = 0; k < (int)slots.size(); ++k)
-                    if (internal(slots[k]) && (best_k < 0 || area(slots[k]) > area(slots[best_k]))) best_k = k;
-                if (best_k < 0) break;
-                const int c = slots[best_k];
-                slots[best_k] = LK[(size_t)c * 4];
-                slots.push_back(LK[(size_t)c * 4 + 1]);
-            }
-            return slots;
+            int s[4];
+            const int n = wide_cut(LK, BD, n2, s);
+            return std::vector<int>(s, s + n);
         };
         nodesq.emplace_back();
         root_wordw = 0;

@@ -43,7 +43,8 @@ extern "C" {
  *    rtg_*_env_sampling, rtg_env_* and rtg_probe_env_samples; rtg_probe_connect; light selection,
  *    rtg_*_light_sampling, rtg_light_* and rtg_probe_light_pick; the material model,
  *    rtg_*_material_model, rtg_*_material_params and rtg_probe_material; path-tracer MIS,
- *    rtg_*_path_mis, rtg_probe_mis_weight, rtg_probe_env_pdf and rtg_light_of_triangle) */
+ *    rtg_*_path_mis, rtg_probe_mis_weight, rtg_probe_env_pdf and rtg_light_of_triangle; rough dielectric
+ *    transmission, RTG_MODEL_ROUGH_DIELECTRIC and rtg_probe_transmission) */
 #define RTG_ABI_VERSION 6
 
 /* error codes */
@@ -406,8 +407,9 @@ int  rtg_light_pick_build(const double* weights, uint32_t n, double uniform_shar
  * untouched: the same kernels, draws and bits. Under RTG_MATERIALS_PHYSICAL a material whose parameter
  * record (rtg_set_material_params, one per rtg_scene_desc.materials entry, in that order) carries the tag
  * RTG_MODEL_CONDUCTOR, _PLASTIC or _ORENNAYAR shades with the model below; a record tagged
- * RTG_MODEL_REFERENCE (diffuse, mirror, glass, and the rough dielectric, which stays the Lambert stub)
- * shades as it does by default. Definition, in the local frame of the shading normal (z; the frame is
+ * RTG_MODEL_REFERENCE (diffuse, mirror, glass, and the rough dielectric where the caller leaves it the
+ * Lambert stub; RTG_MODEL_ROUGH_DIELECTRIC, further below, gives it its own model) shades as it does by
+ * default. Definition, in the local frame of the shading normal (z; the frame is
  * Frame::fromVector's), wo = the direction back along the ray after the two-sided flip, IEEE float32 in
  * the order written, no contraction; pi = (float)M_PI; dot(a, b) = (ax bx + ay by) + az bz:
  *   parameters     alpha = 1.62142f * sqrtf(roughness), formed by the host as the reference's constructors
@@ -474,7 +476,7 @@ int  rtg_light_pick_build(const double* weights, uint32_t n, double uniform_shar
  * Oren-Nayar record: a scene without one keeps today's kernels and bits under both settings. It does not
  * apply to RTG_INTEGRATOR_DIRECT_MIS, _ALBEDO and _NORMALS, to rtg_render_light and
  * rtg_render_instant_radiosity, or to the denoiser's guides: they keep the reference model. Not modelled:
- * rough dielectric transmission, LayeredBSDF. (MIS between NEE and BSDF-sampled emitter hits is
+ * LayeredBSDF (rough dielectric transmission is RTG_MODEL_ROUGH_DIELECTRIC, below). (MIS between NEE and BSDF-sampled emitter hits is
  * rtg_set_path_mis, below; RTG_ALPHA_DELTA and the delta-lobe rule are the same under it.)
  * rtg_set_material_params copies n records (n must equal rtg_scene_desc.n_materials);
  * rtg_material_params_check is its argument check alone (no handle, no device call): a null pointer, a
@@ -491,13 +493,15 @@ int  rtg_light_pick_build(const double* weights, uint32_t n, double uniform_shar
 #define RTG_MODEL_CONDUCTOR 1
 #define RTG_MODEL_PLASTIC   2
 #define RTG_MODEL_ORENNAYAR 3
+/* (4 is left unassigned: rtg_material_params_check rejects it) */
+#define RTG_MODEL_ROUGH_DIELECTRIC 5   /* rough dielectric transmission, below */
 #define RTG_ALPHA_DELTA 0.01f
 typedef struct rtg_material_params {
     int32_t model;                 /* RTG_MODEL_* */
     float alpha;                   /* GGX width, 1.62142f * sqrtf(roughness) (conductor, plastic) */
     float sigma;                   /* Oren-Nayar width */
     float eta[3], k[3];            /* conductor */
-    float int_ior, ext_ior;        /* plastic */
+    float int_ior, ext_ior;        /* plastic, rough dielectric */
 } rtg_material_params;
 int  rtg_material_params_check(const rtg_material_params* params, uint32_t n, uint32_t n_materials);
 int  rtg_set_material_params(rtg_handle* h, const rtg_material_params* params, uint32_t n);
@@ -509,6 +513,80 @@ int  rtg_get_material_model(rtg_handle* h, int* mode);
  * out: n*16 floats (wi.xyz world, colour.rgb, pdf, draws consumed, delta flag, evaluate(query).rgb,
  * PDF(query), pad[3]). A model other than conductor, plastic or Oren-Nayar: RTG_ERR_ARG. */
 int  rtg_probe_material(const float* cases, uint32_t n, float* out);
+
+/* ---- rough dielectric transmission (rtg_shade_trans.hip, rtg_trans.h). RTBase's rough
+ * DielectricBSDF ("bsdf": "dielectric" with roughness >= 0.001) is a stub that shades as a cosine-sampled
+ * Lambertian, and under RTG_MATERIALS_PHYSICAL a record tagged RTG_MODEL_REFERENCE keeps it that way. A
+ * record tagged RTG_MODEL_ROUGH_DIELECTRIC (5; 4 is left unassigned) shades with the microfacet refraction
+ * model of Walter et al. 2007 on the GGX pieces above: alpha, int_ior and ext_ior are the record's.
+ * rth_scene_material_params_transmissive (include/rth.h) hands out the loader's records with that tag;
+ * rth_scene_material_params keeps RTG_MODEL_REFERENCE. Definition, in the local frame of the shading
+ * normal as above, IEEE float32 in the order written, no contraction, with + - * /, sqrtf and sincosf only:
+ *   side           a dielectric is one-sided (rtg_material.two_sided = 0): the shading normal is not flipped
+ *                  and wo.z may be negative. s = wo.z > 0; eta_i = s ? ext_ior : int_ior, eta_t the other.
+ *                  wo' = s ? wo : -wo and wi' = s ? wi : -wi (all three components), so wo'.z > 0; a
+ *                  sampled wi' is mapped back the same way. wo.z == 0 (or not a number): evaluate and PDF
+ *                  are 0 and sample ends the path. A two-sided material tagged 5 has its normal flipped
+ *                  towards wo at every hit, so s is always true: a sheet that is entered from either side
+ *                  and never left.
+ *   F_out(c)       fresnelDielectric (Materials.h:55-77) at clamp01(c), c a cosine on the exterior side, with
+ *                  iorInt = ext_ior, iorExt = int_ior, as GlassBSDF calls it from outside; total internal
+ *                  reflection (an exterior denser than the interior) gives 1.
+ *   F(c)           the interface's Fresnel term for a cosine c on wo's side, the same number from both sides:
+ *                  s: F_out(c). Otherwise, from inside, at the exterior cosine of Snell's law: cc =
+ *                  clamp01(c); r = int_ior / ext_ior; s2 = (r r) (1 - (cc cc)); s2 > 1: 1 (total internal
+ *                  reflection); else F_out(sqrtf(1 - s2)). fresnelDielectric's own value from inside is not
+ *                  used: its perpendicular term divides by (ior cos_i + ior cos_t) where Fresnel has (ior
+ *                  cos_i + cos_t), so it differs between the two sides (0.05125 entering IOR 1.5 at the
+ *                  normal, 0.03389 leaving), and a transmission lobe built on it is not reciprocal.
+ *   reflection     wi'.z > 0: (h, ch) the half vector of (wo', wi') as above (wo' + wi' = 0: 0);
+ *                  f = F(ch) ((D(h) G(wi', wo')) / ((4 wo'.z) wi'.z)); pdf = F(ch) ((G1(wo') D(h)) / (4 wo'.z)).
+ *   transmission   wi'.z < 0: hs = -((wo' eta_i) + (wi' eta_t)); l2 = dot(hs, hs) (!(l2 > 0): 0);
+ *                  h = hs (1 / sqrtf(l2)), negated when h.z < 0; coh = dot(wo', h); cih = dot(wi', h); the
+ *                  lobe is 0 unless coh > 0 and cih < 0. aci = -cih; aiz = -wi'.z; T = 1 - F_out(s ? coh : aci),
+ *                  the half vector's cosine on the exterior side itself;
+ *                  den = (eta_i coh) + (eta_t cih); den2 = den den; et2 = eta_t eta_t; g1o = G1(wo');
+ *                  f = (((coh aci) et2) (T (D(h) (G1(wi') g1o)))) / ((wo'.z aiz) den2);
+ *                  pdf = (T (((g1o coh) D(h)) / wo'.z)) ((et2 aci) / den2).
+ *                  Walter's form without a radiance-compression factor: the lobe integrates to 1 - F, as
+ *                  GlassBSDF's (1 - R) does. wi'.z == 0: 0.
+ *   evaluate, PDF  evaluate = albedo f on every channel, PDF = pdf, on the whole sphere.
+ *   sample         three draws u0, u1, u2, always all three. m = the visible normal ne of wo' for (u1, u2)
+ *                  (the conductor's sampler above up to ne); dm = dot(wo', m); c = clamp01(dm). u0 < F(c):
+ *                  wi' = (m (2 dm)) - wo', kept when wi'.z > 0. Otherwise eta = eta_t / eta_i;
+ *                  k = 1 - ((1 - (c c)) / (eta eta)); a = (c / eta) - sqrtf(k); wi' = (m a) - (wo' / eta),
+ *                  kept when wi'.z < 0. colour = evaluate(wo, wi) and pdf = PDF(wo, wi) by the two functions
+ *                  above from the sampled wi. A wi' that is not kept, or a pdf not in (0, FLT_MAX]: pdf = 0
+ *                  and the path ends at this vertex (its NEE term stays). A kept sample's weight colour
+ *                  |wi.z| / pdf is albedo G1(wi').
+ *   delta limit    alpha < RTG_ALPHA_DELTA: GlassBSDF::sample with the record's IORs (the glass branch of
+ *                  rtg_probe_bsdf: its draws, wi, colour and pdf bit for bit), a delta sample (no cosine
+ *                  factor, canHitLight), no NEE at the vertex; evaluate and PDF are 0. The loader never
+ *                  produces it (roughness < 0.001 is RTG_MAT_GLASS already); a caller's record can.
+ *   in the path    NEE at a tag-5 vertex: the geometry term takes |dot(wi, sN)| where computeDirect has
+ *                  max(dot(wi, sN), 0), for area lights and the environment alike, so a light behind the
+ *                  surface is reached through the transmission lobe; f = evaluate(wo, sd); the shadow ray
+ *                  starts at x + sd EPS, on the side it leaves by. Bounce: thr = ((thr colour) |dot(wi, sN)|)
+ *                  / pdf from x + wi EPS; a non-delta sample does not carry canHitLight. Under
+ *                  RTG_PATH_MIS_POWER p_b = PDF(wo, sd) with both lobes, and the sample's pdf travels in
+ *                  thr.w; the emitter-hit and miss sites are as they are.
+ * With F taken from the exterior side for both directions the transmission lobe is reciprocal up to the
+ * squared indices, f_t(a, b) eta_a^2 = f_t(b, a) eta_b^2 (eta_x the index of the medium x lies in): in the
+ * two evaluations h, den^2, D and the cosine handed to F_out have the same bits. Radiance is not scaled
+ * across the interface. The delta limit is GlassBSDF as it is, with fresnelDielectric's own value per side.
+ * The family (k_shade_trans<ALT, TAB> for PATH and DIRECT, k_shade_trans_mis<TAB> for PATH under
+ * rtg_set_path_mis; it shades conductor, plastic and Oren-Nayar records as k_shade_phys and k_shade_mis do)
+ * is launched only under RTG_MATERIALS_PHYSICAL with RTG_INTEGRATOR_PATH or _DIRECT when the parameter
+ * table holds a tag-5 record that some triangle uses; everything else runs what it ran, with its bits, and
+ * the exclusions are the material model's: _DIRECT_MIS, _ALBEDO, _NORMALS, rtg_render_light,
+ * rtg_render_instant_radiosity and the denoiser's guides keep the reference model. Argument check, beside
+ * the material model's: a tag-5 record whose int_ior or ext_ior is not > 0, or whose int_ior equals its
+ * ext_ior (the lobe collapses to a delta straight through, which the model does not cover), is RTG_ERR_ARG.
+ * Not covered: LayeredBSDF, radiance scaling across the interface, the C oracle, integration/rtg_rtbase.h. */
+/* rtg_probe_material for the rough dielectric (rtg_shade_trans.hip): that probe's layout in and out, int_ior
+ * and ext_ior the record's, wo and the query anywhere on the sphere. A model other than
+ * RTG_MODEL_ROUGH_DIELECTRIC: RTG_ERR_ARG. */
+int  rtg_probe_transmission(const float* cases, uint32_t n, float* out);
 
 /* ---- multiple importance sampling of emitters in the path tracer (rtg_shade_mis.hip,
  * rtg_mis.h). pathTrace (Renderer.h:328-392) counts an emitter hit only after a camera or specular bounce,
@@ -568,8 +646,8 @@ int  rtg_probe_material(const float* cases, uint32_t n, float* out);
  * environment mode, light selection mode and material model and with camera sampling. It does not apply
  * to RTG_INTEGRATOR_DIRECT, _DIRECT_MIS, _ALBEDO and _NORMALS, to rtg_render_light and
  * rtg_render_instant_radiosity, or to the denoiser's guides: they keep today's kernels and bits under
- * either setting. Not covered: rough dielectric transmission, LayeredBSDF, per-shading-point light
- * selection, a lower RTG_ALPHA_DELTA. The setter first issues and waits for queued frames; an unknown
+ * either setting. A rough dielectric record (RTG_MODEL_ROUGH_DIELECTRIC) is covered: p_b is its PDF with both
+ * lobes. Not covered: LayeredBSDF, per-shading-point light selection, a lower RTG_ALPHA_DELTA. The setter first issues and waits for queued frames; an unknown
  * mode is RTG_ERR_ARG, reported before any device call, with the setting and the film left as they were
  * (rtg_path_mis_check is that check alone). The triangle -> light map (int32 per triangle, -1: no light)
  * is built on the host from the light list when the mode is first switched on and kept until

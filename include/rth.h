@@ -57,6 +57,11 @@ int  rth_scene_permutation(const rth_scene* s, uint32_t* out /* n_tris */);
  * keeps intIOR, extIOR and alpha under the tag RTG_MODEL_REFERENCE (no model uses them); every other bsdf:
  * RTG_MODEL_REFERENCE, all parameters 0. The pointer lives as long as the scene. */
 const rtg_material_params* rth_scene_material_params(const rth_scene* s, uint32_t* n /* or NULL */);
+/* The same records with the loader's rough dielectrics ("bsdf": "dielectric" with roughness >= 0.001, kind
+ * RTG_MAT_LAMBERT) tagged RTG_MODEL_ROUGH_DIELECTRIC: what rtg_set_material_params takes for rough
+ * dielectric transmission (include/rtg.h). Every other record equals rth_scene_material_params' field
+ * for field. */
+const rtg_material_params* rth_scene_material_params_transmissive(const rth_scene* s, uint32_t* n /* or NULL */);
 
 /* Film::save: divide the accumulated sum by spp and write RLE RGBE (.hdr). */
 int  rth_save_hdr(const char* path, int32_t width, int32_t height, const float* rgb_sum, uint32_t spp);

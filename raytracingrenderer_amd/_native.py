@@ -23,6 +23,7 @@ RTG_LIGHTS_UNIFORM, RTG_LIGHTS_POWER = 0, 1
 RTG_MATERIALS_REFERENCE, RTG_MATERIALS_PHYSICAL = 0, 1
 RTG_PATH_MIS_OFF, RTG_PATH_MIS_POWER = 0, 1
 RTG_MODEL_REFERENCE, RTG_MODEL_CONDUCTOR, RTG_MODEL_PLASTIC, RTG_MODEL_ORENNAYAR = 0, 1, 2, 3
+RTG_MODEL_ROUGH_DIELECTRIC = 5  # (4 is left unassigned)
 RTG_ALPHA_DELTA = 0.01
 
 f32p = C.POINTER(C.c_float)
@@ -199,6 +200,7 @@ RTG_EXPORTS = [
     ("rtg_group_set_material_params", C.c_int, [C.c_void_p, C.POINTER(rtg_material_params), C.c_uint32]),
     ("rtg_group_set_material_model", C.c_int, [C.c_void_p, C.c_int]),
     ("rtg_probe_material", C.c_int, [f32p, C.c_uint32, f32p]),
+    ("rtg_probe_transmission", C.c_int, [f32p, C.c_uint32, f32p]),
     # path-tracer MIS of emitters (rtg_shade_mis.hip)
     ("rtg_path_mis_check", C.c_int, [C.c_int]),
     ("rtg_set_path_mis", C.c_int, [C.c_void_p, C.c_int]),
@@ -218,6 +220,7 @@ RTH_EXPORTS = [
     ("rth_scene_get_info", C.c_int, [C.c_void_p, C.POINTER(rth_scene_info)]),
     ("rth_scene_permutation", C.c_int, [C.c_void_p, u32p]),
     ("rth_scene_material_params", C.POINTER(rtg_material_params), [C.c_void_p, u32p]),
+    ("rth_scene_material_params_transmissive", C.POINTER(rtg_material_params), [C.c_void_p, u32p]),
     ("rth_save_hdr", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, f32p, C.c_uint32]),
     ("rth_write_hdr", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, f32p]),
     ("rth_read_hdr", C.c_int, [C.c_char_p, i32p, i32p, C.POINTER(f32p)]),

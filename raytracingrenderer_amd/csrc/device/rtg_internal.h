@@ -422,6 +422,7 @@ struct rtg_handle {
     std::vector<rtg_material_params> mat_params;
     bool phys_built = false;                   // the device table holds mat_params
     bool phys_any = false;                     // a triangle has a conductor, plastic or Oren-Nayar record
+    bool trans_any = false;                    // a triangle has a rough dielectric record (k_shade_trans)
     PhysMat* d_phys = nullptr;
     unsigned* d_phys_index = nullptr;
     int n_phys = 0;
@@ -583,6 +584,12 @@ bool path_mis_active(const rtg_handle* h);
 // one k_shade_mis launch (TAB; the tables as runtime arguments, phys with a null table: the reference model)
 int launch_shade_mis(const rtg_handle* h, bool tab, unsigned grid, hipStream_t st, const ChunkArgs& a, const PathBufs& p,
                      int b, const EnvTable& env, const LightPick& pick, const PhysArgs& phys);
+// rtg_shade_trans.hip: RTG_MATERIALS_PHYSICAL, a triangle with a rough dielectric record and PATH or DIRECT:
+// k_shade_trans (under rtg_set_path_mis's PATH: k_shade_trans_mis) in k_shade_phys's / k_shade_mis's place
+bool trans_active(const rtg_handle* h);
+// one launch of that family (phys: phys_args_of's table, which trans_active implies)
+int launch_shade_trans(const rtg_handle* h, bool alt, bool tab, unsigned grid, hipStream_t st, const ChunkArgs& a,
+                       const PathBufs& p, int b, const EnvTable& env, const LightPick& pick, const PhysArgs& phys);
 // RTG_ERR_ARG (with "who: ..." as the message) for records outside include/rtg.h's ranges
 int material_params_check(const char* who, const rtg_material_params* params, uint32_t n, uint32_t n_materials);
 // rtg_shade.hip: one k_shade launch of `grid` blocks (ALT = alt, TAB = tab) for bounce b

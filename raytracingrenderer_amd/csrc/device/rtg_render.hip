@@ -621,7 +621,9 @@ static int issue_chunk(rtg_handle* h, ChunkSlot& sl, const ChunkArgs& a, int max
                 const EnvTable et = env_table_of(h);  // RTG_ENV_LUMINANCE with a table: k_shade_env
                 const LightPick pk = light_pick_of(h);  // RTG_LIGHTS_POWER with a table: k_shade_pick
                 const PhysArgs ph = phys_args_of(h);  // RTG_MATERIALS_PHYSICAL with such a material: k_shade_phys
-                if (path_mis_active(h))  // RTG_PATH_MIS_POWER under PATH: k_shade_mis
+                if (trans_active(h))  // ... with a rough dielectric record: k_shade_trans / k_shade_trans_mis
+                    rc = launch_shade_trans(h, alt, tab && ph.n <= RTG_LDS_PHYS, 8 * tiles, ss, a, pb, b - 1, et, pk, ph);
+                else if (path_mis_active(h))  // RTG_PATH_MIS_POWER under PATH: k_shade_mis
                     rc = launch_shade_mis(h, tab, 8 * tiles, ss, a, pb, b - 1, et, pk, ph);
                 else if (ph.table)
                     rc = launch_shade_phys(alt, tab && ph.n <= RTG_LDS_PHYS, 8 * tiles, ss, h->sv, a, pb, b - 1, et, pk, ph);

@@ -25,6 +25,11 @@
 // or a miss after a non-specular sample is weighted against NEE's density of it (the hit triangle's
 // light comes from a map indexed by the triangle id, loaded beside the shading record). Every statement
 // of it stands inside #ifdef RTG_SHADE_MIS.
+// RTG_SHADE_TRANS defined beside RTG_SHADE_PHYS (k_shade_trans and, with RTG_SHADE_MIS, k_shade_trans_mis,
+// rtg_shade_trans.hip, which includes rtg_trans.h): a record tagged RTG_MODEL_ROUGH_DIELECTRIC shades with
+// the rough dielectric's reflection and transmission lobes: |dot(wi, sN)| in NEE's geometry term, the
+// model's evaluate and PDF on the whole sphere, its sample at the bounce. Every statement of it stands
+// inside #ifdef RTG_SHADE_TRANS.
     __shared__ unsigned s_cnt[2][RTG_TB / 64];
     __shared__ unsigned s_base[2];
     __shared__ float4 s_sho[RTG_TB], s_shd[RTG_TB];  // NEE ray staged until its queue position is known
@@ -328,7 +333,13 @@
                     // a delta conductor takes no light sample; a plastic's base always does
                     const PhysMat& Q0 = TAB ? s_pm[pmi] : pm.table[pmi];
                     ptag = __float_as_int(Q0.a.x);
+#ifdef RTG_SHADE_TRANS
+                    // ... and neither does a delta rough dielectric (GlassBSDF's limit)
+                    const bool tr = ptag == RTG_MODEL_ROUGH_DIELECTRIC;  // |dot(wi, sN)| in the geometry term
+                    if (!spec && !((ptag == RTG_MODEL_CONDUCTOR || tr) && Q0.a.y < RTG_ALPHA_DELTA)) {
+#else
                     if (!spec && !(ptag == RTG_MODEL_CONDUCTOR && Q0.a.y < RTG_ALPHA_DELTA)) {
+#endif
 #else
                     if (!spec) {
 #endif
@@ -357,7 +368,12 @@
                             v3 wi = sub(l_p2, x);
                             const float l2 = length_sq(wi);
                             wi = normalize(wi);
+#ifdef RTG_SHADE_TRANS
+                            l_g = ((tr ? fabsf(dot(wi, sn)) : wmax(dot(wi, sn), 0.0f)) *
+                                   wmax(-dot(wi, mk(L.gn.x, L.gn.y, L.gn.z)), 0.0f)) / l2;
+#else
                             l_g = (wmax(dot(wi, sn), 0.0f) * wmax(-dot(wi, mk(L.gn.x, L.gn.y, L.gn.z)), 0.0f)) / l2;
+#endif
 #ifdef RTG_SHADE_MIS
                             l_pl = pdf_area_to_solid((PICK ? pmf : s.pmf) * l_pdf, l2,
                                                      wmax(-dot(wi, mk(L.gn.x, L.gn.y, L.gn.z)), 0.0f));
@@ -377,7 +393,11 @@
                                 wi = uniform_sample_sphere(q1, q2);
                                 l_pdf = uniform_sphere_pdf();
                             }
+#ifdef RTG_SHADE_TRANS
+                            l_g = ok ? (tr ? fabsf(dot(wi, sn)) : wmax(dot(wi, sn), 0.0f)) : 0.0f;
+#else
                             l_g = ok ? wmax(dot(wi, sn), 0.0f) : 0.0f;  // (a rejected sample: nothing, no shadow ray)
+#endif
                             l_p2 = add(x, muls(wi, 10000.0f));
                             env_dir = wi;  // its radiance: EnvironmentMap::evaluate(wi), below (used iff g > 0)
                             env_need = l_g > 0;
@@ -432,7 +452,14 @@
                     const float maxt = sqrtf(length_sq(sd)) - (2.0f * RTG_EPS);
                     sd = normalize(sd);
                     const v3 so = add(x, muls(sd, RTG_EPS));
-#ifdef RTG_SHADE_PHYS
+#ifdef RTG_SHADE_TRANS
+                    // a rough dielectric's two lobes share their terms with its PDF: one evaluation for both
+                    float tf = 0.0f, tp = 0.0f;
+                    if (ptag == RTG_MODEL_ROUGH_DIELECTRIC) trans_terms(Q, to_local(fr, wo), to_local(fr, sd), tf, tp);
+                    const v3 f = ptag == RTG_MODEL_ROUGH_DIELECTRIC ? muls(alb, tf)
+                                 : ptag != RTG_MODEL_REFERENCE ? phys_eval(Q, alb, to_local(fr, wo), to_local(fr, sd))
+                                                               : divs_pi(alb);
+#elif defined(RTG_SHADE_PHYS)
                     const v3 f = ptag != RTG_MODEL_REFERENCE ? phys_eval(Q, alb, to_local(fr, wo), to_local(fr, sd))
                                                             : divs_pi(alb);
 #else
@@ -441,8 +468,14 @@
                     ld = divs(muls(mul(f, emitted), l_g), PICK ? l_pp : pmf * l_pdf);
 #ifdef RTG_SHADE_MIS
                     {  // weighted against the BSDF's density of the shadow ray's direction
+#ifdef RTG_SHADE_TRANS
+                        const float p_b = ptag == RTG_MODEL_ROUGH_DIELECTRIC ? tp
+                                          : ptag != RTG_MODEL_REFERENCE ? phys_pdf(Q, to_local(fr, wo), to_local(fr, sd))
+                                                                        : bsdf_pdf_lambert(fr, sd);
+#else
                         const float p_b = ptag != RTG_MODEL_REFERENCE ? phys_pdf(Q, to_local(fr, wo), to_local(fr, sd))
                                                                       : bsdf_pdf_lambert(fr, sd);
+#endif
                         ld = muls(ld, mis_w(l_pl, p_b));
                     }
 #endif
@@ -473,6 +506,12 @@
                         // the sample says whether it is specular (a delta lobe) and whether the path lives
                         bool sp = spec, live = true;
                         v3 wi;
+#ifdef RTG_SHADE_TRANS
+                        if (ptag == RTG_MODEL_ROUGH_DIELECTRIC) {
+                            wi = trans_sample(Q, alb, fr, wo, smp, ind, pdf, sp);
+                            live = pdf > 0.0f;
+                        } else
+#endif
                         if (ptag != RTG_MODEL_REFERENCE) {
                             wi = to_world(fr, phys_sample(Q, alb, to_local(fr, wo), smp, ind, pdf, sp));
                             live = pdf > 0.0f;

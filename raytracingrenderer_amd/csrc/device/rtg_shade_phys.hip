@@ -79,13 +79,17 @@ int material_params_check(const char* who, const rtg_material_params* params, ui
     if (n != n_materials) { g_err = std::string(who) + ": one record per scene material is needed"; return RTG_ERR_ARG; }
     for (uint32_t i = 0; i < n; ++i) {
         const rtg_material_params& m = params[i];
-        if (m.model < RTG_MODEL_REFERENCE || m.model > RTG_MODEL_ORENNAYAR) {
+        if ((m.model < RTG_MODEL_REFERENCE || m.model > RTG_MODEL_ORENNAYAR) && m.model != RTG_MODEL_ROUGH_DIELECTRIC) {
             g_err = std::string(who) + ": unknown model tag";
             return RTG_ERR_ARG;
         }
         bool ok = param_ok(m.alpha) && param_ok(m.sigma) && param_ok(m.int_ior) && param_ok(m.ext_ior);
         for (int k = 0; k < 3; ++k) ok = ok && param_ok(m.eta[k]) && param_ok(m.k[k]);
         if (!ok) { g_err = std::string(who) + ": a negative or non-finite parameter"; return RTG_ERR_ARG; }
+        if (m.model == RTG_MODEL_ROUGH_DIELECTRIC && !(m.int_ior > 0.0f && m.ext_ior > 0.0f && m.int_ior != m.ext_ior)) {
+            g_err = std::string(who) + ": a rough dielectric needs int_ior and ext_ior above 0 and unequal";
+            return RTG_ERR_ARG;
+        }
     }
     return RTG_OK;
 }
@@ -117,10 +121,11 @@ static int build_phys_table(rtg_handle* h) {
     }
     if (uniq.empty()) uniq.push_back(record_of(rtg_material_params{}));
     std::vector<unsigned> index(h->tri_mat.size());
-    bool any = false;
+    bool any = false, any_trans = false;
     for (size_t t = 0; t < index.size(); ++t) {
         index[t] = of_mat[h->tri_mat[t]];  // (prepare_scene checked the triangle's material index)
         any = any || h->mat_params[h->tri_mat[t]].model != RTG_MODEL_REFERENCE;
+        any_trans = any_trans || h->mat_params[h->tri_mat[t]].model == RTG_MODEL_ROUGH_DIELECTRIC;
     }
     PhysMat* d_tab = nullptr;
     unsigned* d_idx = nullptr;
@@ -141,6 +146,7 @@ static int build_phys_table(rtg_handle* h) {
     h->d_phys_index = d_idx;
     h->n_phys = (int)uniq.size();
     h->phys_any = any;
+    h->trans_any = any_trans;
     h->phys_built = true;
     h->phys_index.swap(index);
     return mis_sync_tables(h);  // (rtg_set_path_mis's table holds a copy of the index)

@@ -34,7 +34,9 @@
 // Material model (rtg_set_material_model): -materials reference|physical (reference: conductor, plastic
 // and Oren-Nayar materials shade as the reference's Lambertian stubs; physical: GGX conductor, coated
 // plastic and Oren-Nayar from the scene's own roughness, eta, k, IORs and alpha), for one device and for
-// -gpus / -devices alike.
+// -gpus / -devices alike. -transmission 0|1 (default 0; needs -materials physical): 1 shades the scene's
+// rough dielectrics with GGX reflection and refraction (rth_scene_material_params_transmissive) instead
+// of the Lambertian stub.
 // Path-tracer MIS (rtg_set_path_mis): -pathMIS off|power (off: the reference's pathTrace; power: NEE and
 // BSDF-sampled emitter hits combined with the power heuristic, a miss weighted by the throughput), for one
 // device and for -gpus / -devices alike.
@@ -125,11 +127,15 @@ int main(int argc, char** argv) {
     const std::string mtl = get("-materials", "reference");
     if (mtl != "reference" && mtl != "physical") return die("-materials", "one of reference, physical");
     const bool physical = mtl == "physical";
+    const std::string trn = get("-transmission", "0");
+    if (trn != "0" && trn != "1") return die("-transmission", "one of 0, 1");
+    if (trn == "1" && !physical) return die("-transmission", "needs -materials physical");
     const std::string pmn = get("-pathMIS", "off");
     if (pmn != "off" && pmn != "power") return die("-pathMIS", "one of off, power");
     const int path_mis = pmn == "power" ? RTG_PATH_MIS_POWER : RTG_PATH_MIS_OFF;
     uint32_t n_params = 0;
-    const rtg_material_params* params = rth_scene_material_params(scene, &n_params);
+    const rtg_material_params* params = trn == "1" ? rth_scene_material_params_transmissive(scene, &n_params)
+                                                   : rth_scene_material_params(scene, &n_params);
     rtg_handle* rt = nullptr;
     rtg_group* grp = nullptr;
     if (devices.empty()) {

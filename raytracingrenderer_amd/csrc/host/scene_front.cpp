@@ -88,6 +88,7 @@ struct rth_scene {
     std::vector<int32_t> node_links;
     std::vector<rtg_material> materials;
     std::vector<rtg_material_params> mat_params;  // what the BSDF constructors take, one per material
+    std::vector<rtg_material_params> mat_params_trans;  // ... with the rough dielectrics tagged RTG_MODEL_ROUGH_DIELECTRIC
     std::vector<rth::TexData> tex;
     std::vector<rtg_texture> textures;
     std::vector<int32_t> lights;
@@ -353,7 +354,8 @@ static bool load_scene(const std::string& dir, const rth_load_options& o, rth_sc
             mp.model = RTG_MODEL_ORENNAYAR;
             mp.sigma = inst.material.find("alpha").as_float(1.0f);
         } else if (bsdf == "dielectric" && m.kind == RTG_MAT_LAMBERT) {
-            // the rough DielectricBSDF's arguments, kept although no model uses them (it stays the stub)
+            // the rough DielectricBSDF's arguments: the stub's tag here (no model of this accessor uses them),
+            // RTG_MODEL_ROUGH_DIELECTRIC in rth_scene_material_params_transmissive's copy
             mp.int_ior = m.int_ior;
             mp.ext_ior = m.ext_ior;
             mp.alpha = 1.62142f * sqrtf(inst.material.find("roughness").as_float(1.0f));
@@ -365,6 +367,8 @@ static bool load_scene(const std::string& dir, const rth_load_options& o, rth_sc
         uint32_t mat_index = (uint32_t)s->materials.size();
         s->materials.push_back(m);
         s->mat_params.push_back(mp);
+        if (bsdf == "dielectric" && m.kind == RTG_MAT_LAMBERT) mp.model = RTG_MODEL_ROUGH_DIELECTRIC;
+        s->mat_params_trans.push_back(mp);
 
         M4 xf;
         std::memcpy(xf.m, inst.world, sizeof(xf.m));
@@ -565,6 +569,10 @@ const rtg_material_params* rth_scene_material_params(const rth_scene* s, uint32_
     if (!s) return nullptr;
     if (n) *n = (uint32_t)s->mat_params.size();
     return s->mat_params.data();
+}
+const rtg_material_params* rth_scene_material_params_transmissive(const rth_scene* s, uint32_t* n) {
+    if (n) *n = s ? (uint32_t)s->mat_params_trans.size() : 0u;
+    return s ? s->mat_params_trans.data() : nullptr;
 }
 
 int rth_scene_permutation(const rth_scene* s, uint32_t* out) {

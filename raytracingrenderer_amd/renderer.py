@@ -91,6 +91,15 @@ class Scene:
         p = N.rth().rth_scene_material_params(self._h, C.byref(n))
         return [N.rtg_material_params.from_buffer_copy(p[i]) for i in range(n.value)]  # (copies: they outlive the scene)
 
+    @property
+    def material_params_transmissive(self):
+        """material_params with the loader's rough dielectrics tagged RTG_MODEL_ROUGH_DIELECTRIC
+        (rth_scene_material_params_transmissive): what set_material_model("physical", transmission=True)
+        passes on. Every other record equals material_params' field for field."""
+        n = C.c_uint32()
+        p = N.rth().rth_scene_material_params_transmissive(self._h, C.byref(n))
+        return [N.rtg_material_params.from_buffer_copy(p[i]) for i in range(n.value)]
+
     def texture(self, i):
         t = self.desc.textures[i]
         return self._view(t.texels, t.width * t.height * 3, np.float32).reshape(t.height, t.width, 3)
@@ -248,7 +257,8 @@ def _light_sampling(mode, uniform_share):
 
 
 MATERIAL_MODELS = {"reference": N.RTG_MATERIALS_REFERENCE, "physical": N.RTG_MATERIALS_PHYSICAL}
-MODEL_TAGS = {"conductor": N.RTG_MODEL_CONDUCTOR, "plastic": N.RTG_MODEL_PLASTIC, "orennayar": N.RTG_MODEL_ORENNAYAR}
+MODEL_TAGS = {"conductor": N.RTG_MODEL_CONDUCTOR, "plastic": N.RTG_MODEL_PLASTIC, "orennayar": N.RTG_MODEL_ORENNAYAR,
+              "rough_dielectric": N.RTG_MODEL_ROUGH_DIELECTRIC}
 
 
 def _material_model(mode):
@@ -298,6 +308,44 @@ def _material_params_array(params):
     """A ctypes array of rtg_material_params from a sequence of them."""
     params = list(params)
     return (N.rtg_material_params * max(len(params), 1))(*params), len(params)
+
+
+def _material_params_choice(rt, m, transmission, setter, handle):
+    """set_material_model's parameter hand-over for a RayTracer or a RayTracerGroup: the scene's records
+    (the transmissive set when asked for) go to the library before the first "physical" setting and again
+    when the choice changes."""
+    want = bool(transmission)
+    if want and m != N.RTG_MATERIALS_PHYSICAL:
+        raise ValueError("transmission=True needs the \"physical\" material model")
+    if m != N.RTG_MATERIALS_PHYSICAL:
+        return
+    if getattr(rt, "_material_params_set", False) and getattr(rt, "_material_params_trans", False) == want:
+        return
+    arr, n = _material_params_array(rt.scene.material_params_transmissive if want else rt.scene.material_params)
+    _check(setter(handle, arr, n), rt._lib.rtg_last_error)
+    rt._material_params_set = True
+    rt._material_params_trans = want
+
+
+def transmission_probe(wo, draws, query, alpha=0.5, int_ior=1.5, ext_ior=1.0, albedo=(1.0, 1.0, 1.0),
+                       normal=(0.0, 0.0, 1.0)):
+    """The rough dielectric kernels' own sample / evaluate / PDF (rtg_probe_transmission, test surface) on
+    the current device, as material_probe: wo (n, 3), draws (n, 3) and query (n, 3) per case, world space,
+    anywhere on the sphere, with one parameter set, albedo and shading normal for all. Returns
+    material_probe's dict."""
+    wo, dr, qi = (np.ascontiguousarray(v, np.float32).reshape(-1, 3) for v in (wo, draws, query))
+    if not len(wo) == len(dr) == len(qi):
+        raise ValueError("transmission_probe: wo, draws and query must have one length")
+    c = np.zeros((len(wo), 28), np.float32)
+    c[:, 0:5] = (N.RTG_MODEL_ROUGH_DIELECTRIC, alpha, 0.0, int_ior, ext_ior)
+    c[:, 11:14], c[:, 14:17] = albedo, normal
+    c[:, 17:20], c[:, 20:23], c[:, 23:26] = wo, dr, qi
+    out = np.zeros((len(wo), 16), np.float32)
+    lib = N.rtg()
+    _check(lib.rtg_probe_transmission(N.ptr(c, C.c_float), len(c), N.ptr(out, C.c_float)), lib.rtg_last_error)
+    return {"wi": out[:, 0:3].copy(), "colour": out[:, 3:6].copy(), "pdf": out[:, 6].copy(),
+            "draws": out[:, 7].astype(np.int32), "delta": out[:, 8] != 0, "evaluate": out[:, 9:12].copy(),
+            "PDF": out[:, 12].copy()}
 
 
 def material_params_check(params, n_materials):
@@ -482,7 +530,7 @@ class RayTracer:
         return {"prob": e[:, 0].copy(), "alias": u[:, 1].copy(), "pmf_self": e[:, 2].copy(),
                 "pmf_alias": e[:, 3].copy(), "entries": u.copy(), "weights": wt, "build_ms": ms.value}
 
-    def set_material_model(self, mode="reference"):
+    def set_material_model(self, mode="reference", transmission=False):
         """How conductor, plastic and Oren-Nayar materials shade (rtg_set_material_model). "reference"
         (default): as RTBase's stubs do, a cosine-sampled Lambertian, the reference's films bit for bit.
         "physical": a GGX conductor with the material's eta and k, a dielectric GGX coat over the diffuse
@@ -491,12 +539,12 @@ class RayTracer:
         handed to the library here. Applies to render(), adaptiveRender() and the "path" and "direct"
         integrators; "direct_mis", "albedo", "normals", lightTracer(), instantRadiosity() and the
         denoiser's guides keep the reference model. A scene without such a material renders the same
-        film under both."""
+        film under both. transmission=True (with "physical" only) hands the library
+        Scene.material_params_transmissive instead: the scene's rough dielectrics shade with GGX reflection
+        and refraction (RTG_MODEL_ROUGH_DIELECTRIC) in place of the Lambertian stub; False is the call as it
+        was, record for record, and a change of the choice hands the other set."""
         m = _material_model(mode)
-        if m == N.RTG_MATERIALS_PHYSICAL and not getattr(self, "_material_params_set", False):
-            arr, n = _material_params_array(self.scene.material_params)
-            _check(self._lib.rtg_set_material_params(self._h, arr, n), self._lib.rtg_last_error)
-            self._material_params_set = True
+        _material_params_choice(self, m, transmission, self._lib.rtg_set_material_params, self._h)
         _check(self._lib.rtg_set_material_model(self._h, m), self._lib.rtg_last_error)
 
     def material_model(self):
@@ -506,6 +554,7 @@ class RayTracer:
         return {v: k for k, v in MATERIAL_MODELS.items()}.get(m.value, m.value)
 
     material_probe = staticmethod(material_probe)
+    transmission_probe = staticmethod(transmission_probe)
 
     def set_path_mis(self, mode="off"):
         """Multiple importance sampling of emitters in the path tracer (rtg_set_path_mis). "off"
@@ -788,13 +837,10 @@ class RayTracerGroup:
         """RayTracer.set_path_mis on every rank (rtg_group_set_path_mis)."""
         _check(self._lib.rtg_group_set_path_mis(self._g, _path_mis(mode)), self._lib.rtg_last_error)
 
-    def set_material_model(self, mode="reference"):
+    def set_material_model(self, mode="reference", transmission=False):
         """RayTracer.set_material_model on every rank (rtg_group_set_material_params / _model)."""
         m = _material_model(mode)
-        if m == N.RTG_MATERIALS_PHYSICAL and not getattr(self, "_material_params_set", False):
-            arr, n = _material_params_array(self.scene.material_params)
-            _check(self._lib.rtg_group_set_material_params(self._g, arr, n), self._lib.rtg_last_error)
-            self._material_params_set = True
+        _material_params_choice(self, m, transmission, self._lib.rtg_group_set_material_params, self._g)
         _check(self._lib.rtg_group_set_material_model(self._g, m), self._lib.rtg_last_error)
 
     def setup_ms(self):

@@ -44,7 +44,8 @@ extern "C" {
  *    rtg_*_light_sampling, rtg_light_* and rtg_probe_light_pick; the material model,
  *    rtg_*_material_model, rtg_*_material_params and rtg_probe_material; path-tracer MIS,
  *    rtg_*_path_mis, rtg_probe_mis_weight, rtg_probe_env_pdf and rtg_light_of_triangle; rough dielectric
- *    transmission, RTG_MODEL_ROUGH_DIELECTRIC and rtg_probe_transmission) */
+ *    transmission, RTG_MODEL_ROUGH_DIELECTRIC and rtg_probe_transmission; a movable camera, rtg_*_camera;
+ *    the geometry guide and temporal accumulation, rtg_geometry_guide and rtg_temporal_*) */
 #define RTG_ABI_VERSION 6
 
 /* error codes */
@@ -667,6 +668,91 @@ int  rtg_probe_env_pdf(rtg_handle* h, const float* dirs /* n*3 */, uint32_t n, f
 /* The host copy of the triangle -> light map. Before the first RTG_PATH_MIS_POWER setting: RTG_ERR_ARG. */
 int  rtg_light_of_triangle(rtg_handle* h, int32_t* out /* n_triangles */);
 
+/* ---- a movable camera (rtg_api.hip). The camera enters with rtg_scene_desc at rtg_create;
+ * rtg_set_camera replaces both records on a live handle, so a frame loop that moves its camera
+ * (Main.cpp:82-111: W/S/A/D/E/Q, then rt.clear()) keeps the handle, its tree and its upload.
+ * rth_camera_look_at (include/rth.h) builds the records from a pose with the loader's own code.
+ *   - Both records are required and every field of both must be finite; cam->width and cam->height must
+ *     equal the handle's film size. Otherwise RTG_ERR_ARG, reported before any device call, and the camera,
+ *     the film and every setting stay as they were.
+ *   - Frames queued earlier (rtg_render_async) render with the camera they were queued under: the setter
+ *     first issues and waits for them, as rtg_set_camera_sampling does.
+ *   - The film and Film::SPP are left alone: the caller clears them (rtg_clear), as Main.cpp does.
+ *   - The denoiser's cached guides are dropped and rendered again by the next rtg_denoise / rtg_denoise_guides.
+ *   - From the next call on the new records are used by rtg_render, rtg_render_async and the group calls in
+ *     both camera modes of rtg_set_camera_sampling and under every integrator (albedo and normals included),
+ *     by rtg_render_adaptive, rtg_render_light and rtg_render_instant_radiosity (projectOntoCamera),
+ *     rtg_probe_camera_samples, rtg_probe_connect, rtg_geometry_guide and rtg_temporal_accumulate.
+ * rtg_get_camera returns the records in use (either pointer may be NULL). rtg_group_set_camera is
+ * rtg_set_camera on every rank's handle, checked once for all ranks. No kernel is added or changed by
+ * these calls: the kernels take the camera by value with every launch. */
+int  rtg_set_camera(rtg_handle* h, const rtg_camera* cam, const rtg_camera_proj* proj);
+int  rtg_get_camera(rtg_handle* h, rtg_camera* cam, rtg_camera_proj* proj);
+
+/* ---- geometry guide and temporal accumulation by reprojection (rtg_temporal.hip,
+ * tests/temporal_ref.py restates both in numpy). IEEE float32 in the order written, no contraction, plain
+ * /, sqrtf and floorf; dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z.
+ * rtg_geometry_guide: for every pixel the pinhole ray through the pixel centre (Camera::generateRay at
+ * (x + 0.5, y + 0.5), whatever rtg_set_camera_sampling says, as the denoiser's guides) is traced by the
+ * existing generate and traversal kernels; with (t, id) its closest hit, o the camera origin and d its
+ * direction a small kernel writes two 16-byte records per pixel:
+ *   pos_t[p]     = {X.xyz, t},   X = o + d t component-wise (Ray::at: the product, then the sum)
+ *   normal_id[p] = {Ng.xyz, id as bits},  with v0, v1, v2 the triangle's positions (rtg_scene_desc.positions),
+ *                  e1 = v1 - v0, e2 = v2 - v0, c = (e1.y e2.z - e1.z e2.y, e1.z e2.x - e1.x e2.z,
+ *                  e1.x e2.y - e1.y e2.x), l = sqrtf((c.x c.x + c.y c.y) + c.z c.z), Ng = c / l (three divisions)
+ *   a miss:      X = 0, t = FLT_MAX (3.40282347e+38f), Ng = 0, id = -1.
+ * One guide is cached per camera (a byte comparison of both records) in the temporal state. The film,
+ * Film::SPP, the integrator, the options and the statistics are left as they were; the call issues and waits
+ * for queued frames first. Either output may be NULL.
+ * rtg_temporal_accumulate blends the film's mean into a per-pixel history that follows the camera. The state
+ * (allocated by the first call, freed by rtg_destroy, dropped by rtg_temporal_reset) holds the history
+ * H[p] = {rgb, len} (16 B per pixel), the camera records it belongs to, and that camera's guide. The film
+ * is expected to hold only samples not handed over yet: the loop is move, clear, render, accumulate.
+ *   cur[p] = film[p] / m per channel, m = (float)spp; spp == 0: RTG_ERR_ARG.
+ *   no history yet     hist is absent for every pixel; the guide of the current camera is computed and kept.
+ *   camera unchanged   (both records equal the history's byte for byte) hist = H[p] for every pixel, miss
+ *                      pixels included; nothing is traced.
+ *   camera moved       the current guide G is computed. A pixel whose G is a miss (id < 0) has no history.
+ *                      Otherwise X = G.X, N = G.Ng, t = G.t, and X is projected with the *history's* records by
+ *                      Camera::projectOntoCamera's own operations (Scene.h:55-69): pv = cameraToView.mulPoint(X),
+ *                      v1 = the first three rows of proj applied to pv, w = 1.0f / ((((q12 pv.x) + (q13 pv.y)) +
+ *                      (q14 pv.z)) + q15), pp = v1 w, x = (pp.x + 1) 0.5, y = (pp.y + 1) 0.5; rejected (no
+ *                      history) when x < 0, x > 1, y < 0 or y > 1; then x = x width, y = (1 - y) height.
+ *                      u = x - 0.5f, v = y - 0.5f, x0 = floorf(u), y0 = floorf(v), ax = u - x0, ay = v - y0.
+ *                      Four taps, dy = 0, 1 outer and dx = 0, 1 inner: q = (x0 + dx, y0 + dy) (the sums in
+ *                      float), weight w = (dx ? ax : 1 - ax) (dy ? ay : 1 - ay). A tap is used only if
+ *                      0 <= q.x < width and 0 <= q.y < height (as float comparisons: a NaN fails), w > 0, the
+ *                      history's guide at q is a hit, |dot(X_hist[q] - X, N)| <= plane_tolerance t and
+ *                      |dot(Ng_hist[q], N)| >= normal_cos. Used taps: sw = sw + w; acc = acc + w H[q] on all
+ *                      four components. sw > 0: hist = acc / sw (four divisions); otherwise no history.
+ *   blend              with history: n = hist.len < max_history ? hist.len : max_history; a = m / (n + m);
+ *                      out = hist.rgb + (cur - hist.rgb) a; len = n + m. Without: out = cur, len = m.
+ *   update             H[p] = {out, len}; after a move (and on the first call) the stored camera and guide
+ *                      become the current ones.
+ * Non-finite values follow the definition as written: it is not a NaN filter. max_history must be > 0 and may
+ * be +inf (the plain running mean); plane_tolerance >= 0 and finite; normal_cos in [0, 1]; anything else, a
+ * NaN included, is RTG_ERR_ARG before any device call (rtg_temporal_check is that check alone, no device
+ * needed). The defaults (64, 0.01f, 0.9f) are choices, not measured optima. The film, Film::SPP, the
+ * integrator, the options and the statistics are left as they were. The call issues and waits for queued
+ * frames, runs the guide pass and k_temporal on the handle's stream with no host wait in between, and returns
+ * when the result is in the handle's device buffer, and in out (host, w*h*3) when given.
+ * rtg_temporal_history copies H (w*h*4; RTG_ERR_ARG before the first accumulate); rtg_temporal_copy_device the
+ * last result (w*h*3 floats, device to device); rtg_temporal_ms the device time of the last call's guide pass
+ * (0 when none ran) and of its k_temporal launch. Not covered: miss pixels after a move (the background is not
+ * reprojected: they restart), groups (rtg_group_set_camera only), chaining into rtg_denoise on the device,
+ * variance-guided weights, moving geometry. */
+typedef struct rtg_temporal_params {
+    float max_history, plane_tolerance, normal_cos;
+} rtg_temporal_params;
+int  rtg_temporal_defaults(rtg_temporal_params* p);  /* 64, 0.01f, 0.9f */
+int  rtg_temporal_check(const rtg_temporal_params* p);
+int  rtg_geometry_guide(rtg_handle* h, float* pos_t /* w*h*4 */, float* normal_id /* w*h*4 */);
+int  rtg_temporal_accumulate(rtg_handle* h, const rtg_temporal_params* p, float* out /* w*h*3 or NULL */);
+int  rtg_temporal_history(rtg_handle* h, float* rgb_len /* w*h*4 */);
+int  rtg_temporal_copy_device(rtg_handle* h, void* dst_device);
+int  rtg_temporal_reset(rtg_handle* h);
+int  rtg_temporal_ms(rtg_handle* h, double* guide_ms, double* accumulate_ms);
+
 /* Add samples [first_sample, first_sample+n_samples) of every pixel in the listed 32x32 tiles
  * (tile id = ty*tilesX + tx, RTBase TILE_SIZE=32; tile_ids=NULL = all tiles) to the film, in
  * sample order per pixel. Equivalent to n_samples calls of RayTracer::render() with the
@@ -761,6 +847,7 @@ int  rtg_group_set_light_sampling(rtg_group* g, const rtg_light_sampling* p);  /
 int  rtg_group_set_material_params(rtg_group* g, const rtg_material_params* params, uint32_t n);  /* every rank's */
 int  rtg_group_set_material_model(rtg_group* g, int mode);  /* rtg_set_material_model on every rank's handle */
 int  rtg_group_set_path_mis(rtg_group* g, int mode);  /* rtg_set_path_mis on every rank's handle */
+int  rtg_group_set_camera(rtg_group* g, const rtg_camera* cam, const rtg_camera_proj* proj);  /* every rank's handle */
 int  rtg_group_render(rtg_group* g, uint32_t first_sample, uint32_t n_samples, uint64_t seed);
 int  rtg_group_reduce(rtg_group* g);  /* the films stay per device; the assembled film goes to a separate buffer */
 /* Queued forms (the frame loop of Main.cpp:74-118 on N devices). rtg_group_render_async is every

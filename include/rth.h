@@ -63,6 +63,19 @@ const rtg_material_params* rth_scene_material_params(const rth_scene* s, uint32_
  * for field. */
 const rtg_material_params* rth_scene_material_params_transmissive(const rth_scene* s, uint32_t* n /* or NULL */);
 
+/* The camera of loadScene (SceneLoader.h:242-260) from a pose: the code rth_load_scene itself runs on
+ * scene.json's "from", "to", "up", "fov" and "flipX" (Matrix::perspective(0.001f, 10000.0f, width / height,
+ * fov), Matrix::lookAt(from, to, up).invert(), P.m[0] negated when flip_x == 1, then Camera::init /
+ * updateView), so the records of a loaded scene's own pose and size are rtg_scene_desc.camera and
+ * .projection byte for byte. They are what rtg_set_camera (include/rtg.h) takes. RTG_ERR_ARG, with the
+ * outputs left as they were: a null pointer, a non-finite from, to, up or fov, from == to (or a distance
+ * that overflows), up parallel to from - to (up x normalize(from - to) zero or overflowed), width or
+ * height <= 0. */
+int  rth_camera_look_at(const float from[3], const float to[3], const float up[3], float fov_degrees, int32_t width,
+                        int32_t height, int32_t flip_x, rtg_camera* cam, rtg_camera_proj* proj);
+/* What the loaded scene.json said (defaults: fov 45, flipX 0, vectors 0); any output may be NULL. */
+int  rth_scene_camera_pose(const rth_scene* s, float from[3], float to[3], float up[3], float* fov, int32_t* flip_x);
+
 /* Film::save: divide the accumulated sum by spp and write RLE RGBE (.hdr). */
 int  rth_save_hdr(const char* path, int32_t width, int32_t height, const float* rgb_sum, uint32_t spp);
 /* Film::tonemap (Imaging.h:233-242) for every pixel: (sum*exposure/(float)spp) clamped at 0,

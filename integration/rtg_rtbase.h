@@ -2,7 +2,7 @@
 // reference to render on the MI355X (INTEGRATION.md §2 shows this file; it is the compiled code).
 //
 // Include it after RTBase's own headers (Scene.h pulls in Geometry.h, Materials.h, Lights.h,
-// Imaging.h) with include/ on the include path and link -lrtg. Three functions:
+// Imaging.h) with include/ on the include path and link -lrtg. Four functions:
 //
 //   rtg_flatten_scene(scene, binding)   RTBase's built Scene (Scene.h:72-106, after Scene::build:
 //                                       triangles in post-sort order, Scene::lights in reference
@@ -13,6 +13,9 @@
 //                                       run side by side; the call returns at once)
 //   rtg_film_sync(gpu, film)            Film::film brought up to date (waits for the queued frames):
 //                                       before saveHDR / savePNG / presentFilmToCanvas
+//
+//   rtg_update_camera(gpu, scene)       after the camera moved (Main.cpp:82-111): Scene::camera's records
+//                                       handed to the live handle (rtg_set_camera); then clear, as Main.cpp does
 //
 // RayTracer::init (Renderer.h:45-63) then creates the handle once:
 //     rtg_flatten_scene(scene, binding);
@@ -55,6 +58,23 @@ inline void rtg_flatten_bvh(BVHNode* n, std::vector<BVHNode*>& out) {
     out.push_back(n);
     if (n->l) rtg_flatten_bvh(n->l, out);
     if (n->r) rtg_flatten_bvh(n->r, out);
+}
+
+// Camera (Scene.h:10-70) -> the two camera records of include/rtg.h.
+inline void rtg_camera_records(Camera& c, rtg_camera& cam, rtg_camera_proj& proj) {
+    std::memcpy(cam.inv_proj, c.inverseProjectionMatrix.m, 64);
+    std::memcpy(cam.camera, c.camera.m, 64);
+    cam.origin[0] = c.origin.x;
+    cam.origin[1] = c.origin.y;
+    cam.origin[2] = c.origin.z;
+    cam.width = c.width;
+    cam.height = c.height;
+    std::memcpy(proj.proj, c.projectionMatrix.m, 64);  // light tracing (ABI version 2)
+    std::memcpy(proj.camera_to_view, c.cameraToView.m, 64);
+    proj.view_direction[0] = c.viewDirection.x;
+    proj.view_direction[1] = c.viewDirection.y;
+    proj.view_direction[2] = c.viewDirection.z;
+    proj.a_film = c.Afilm;
 }
 
 inline void rtg_flatten_scene(Scene* s, RtgSceneBinding& b) {
@@ -125,20 +145,17 @@ inline void rtg_flatten_scene(Scene* s, RtgSceneBinding& b) {
     d.textures = b.texs.data();
     d.n_lights = (uint32_t)b.lights.size();
     d.lights = b.lights.data();
-    Camera& c = s->camera;
-    std::memcpy(d.camera.inv_proj, c.inverseProjectionMatrix.m, 64);
-    std::memcpy(d.camera.camera, c.camera.m, 64);
-    d.camera.origin[0] = c.origin.x;
-    d.camera.origin[1] = c.origin.y;
-    d.camera.origin[2] = c.origin.z;
-    d.camera.width = c.width;
-    d.camera.height = c.height;
-    std::memcpy(d.projection.proj, c.projectionMatrix.m, 64);  // light tracing (ABI version 2)
-    std::memcpy(d.projection.camera_to_view, c.cameraToView.m, 64);
-    d.projection.view_direction[0] = c.viewDirection.x;
-    d.projection.view_direction[1] = c.viewDirection.y;
-    d.projection.view_direction[2] = c.viewDirection.z;
-    d.projection.a_film = c.Afilm;
+    rtg_camera_records(s->camera, d.camera, d.projection);
+}
+
+// After viewcamera has moved the scene's camera (Main.cpp:82-111: W/S/A/D/E/Q call
+// Camera::updateView through RTCamera, then rt.clear()): the same two records, handed to the live
+// handle. Follow it with rtg_clear(gpu) and film->clear(), as Main.cpp follows it with rt.clear().
+inline int rtg_update_camera(rtg_handle* gpu, Scene* s) {
+    rtg_camera cam{};
+    rtg_camera_proj proj{};
+    rtg_camera_records(s->camera, cam, proj);
+    return rtg_set_camera(gpu, &cam, &proj);
 }
 
 // RayTracer::render() (Renderer.h:876-885): one frame = one sample of every pixel, all tiles,

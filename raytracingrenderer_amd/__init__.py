@@ -4,7 +4,7 @@ The hot path (RayTracer::render) runs as HIP kernels in lib/librtg.so behind inc
 scene loading / BVH build / HDR output run in lib/librth.so behind include/rth.h.
 """
 from .renderer import (NativeError, RayTracer, RayTracerGroup, Scene, denoise_images, loadScene,  # noqa: F401
-                       probe_texture, read_hdr, save_hdr, save_png, tonemap, write_synthetic_scene)
+                       look_at, probe_texture, read_hdr, save_hdr, save_png, tonemap, write_synthetic_scene)
 
 __all__ = ["RayTracer", "RayTracerGroup", "Scene", "loadScene", "save_hdr", "save_png", "tonemap", "read_hdr",
-           "write_synthetic_scene", "NativeError", "denoise_images", "probe_texture"]
+           "write_synthetic_scene", "NativeError", "denoise_images", "probe_texture", "look_at"]

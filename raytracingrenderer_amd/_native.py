@@ -92,6 +92,10 @@ class rtg_material_params(C.Structure):
                 ("k", C.c_float * 3), ("int_ior", C.c_float), ("ext_ior", C.c_float)]
 
 
+class rtg_temporal_params(C.Structure):
+    _fields_ = [("max_history", C.c_float), ("plane_tolerance", C.c_float), ("normal_cos", C.c_float)]
+
+
 class rth_load_options(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("skip_missing", C.c_int32),
                 ("bvh_threads", C.c_int32), ("envmap", C.c_char_p)]
@@ -209,6 +213,19 @@ RTG_EXPORTS = [
     ("rtg_probe_mis_weight", C.c_int, [f32p, f32p, C.c_uint32, f32p]),
     ("rtg_probe_env_pdf", C.c_int, [C.c_void_p, f32p, C.c_uint32, f32p]),
     ("rtg_light_of_triangle", C.c_int, [C.c_void_p, i32p]),
+    # a movable camera (rtg_api.hip)
+    ("rtg_set_camera", C.c_int, [C.c_void_p, C.POINTER(rtg_camera), C.POINTER(rtg_camera_proj)]),
+    ("rtg_get_camera", C.c_int, [C.c_void_p, C.POINTER(rtg_camera), C.POINTER(rtg_camera_proj)]),
+    ("rtg_group_set_camera", C.c_int, [C.c_void_p, C.POINTER(rtg_camera), C.POINTER(rtg_camera_proj)]),
+    # the geometry guide and temporal accumulation by reprojection (rtg_temporal.hip)
+    ("rtg_temporal_defaults", C.c_int, [C.POINTER(rtg_temporal_params)]),
+    ("rtg_temporal_check", C.c_int, [C.POINTER(rtg_temporal_params)]),
+    ("rtg_geometry_guide", C.c_int, [C.c_void_p, f32p, f32p]),
+    ("rtg_temporal_accumulate", C.c_int, [C.c_void_p, C.POINTER(rtg_temporal_params), f32p]),
+    ("rtg_temporal_history", C.c_int, [C.c_void_p, f32p]),
+    ("rtg_temporal_copy_device", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("rtg_temporal_reset", C.c_int, [C.c_void_p]),
+    ("rtg_temporal_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 ]
 
 RTH_EXPORTS = [
@@ -221,6 +238,9 @@ RTH_EXPORTS = [
     ("rth_scene_permutation", C.c_int, [C.c_void_p, u32p]),
     ("rth_scene_material_params", C.POINTER(rtg_material_params), [C.c_void_p, u32p]),
     ("rth_scene_material_params_transmissive", C.POINTER(rtg_material_params), [C.c_void_p, u32p]),
+    ("rth_camera_look_at", C.c_int, [f32p, f32p, f32p, C.c_float, C.c_int32, C.c_int32, C.c_int32,
+                                     C.POINTER(rtg_camera), C.POINTER(rtg_camera_proj)]),
+    ("rth_scene_camera_pose", C.c_int, [C.c_void_p, f32p, f32p, f32p, f32p, i32p]),
     ("rth_save_hdr", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, f32p, C.c_uint32]),
     ("rth_write_hdr", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, f32p]),
     ("rth_read_hdr", C.c_int, [C.c_char_p, i32p, i32p, C.POINTER(f32p)]),

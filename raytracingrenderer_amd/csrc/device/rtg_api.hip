@@ -4,6 +4,7 @@
 #include "rtg_internal.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 thread_local std::string g_err;
@@ -147,6 +148,24 @@ int upload_scene(int device, const HostScene& hs, rtg_handle* h) {
     return ensure_ovf(h, h->slot[0]);
 }
 
+int camera_check(const char* who, const rtg_handle* h, const rtg_camera* cam, const rtg_camera_proj* proj) {
+    auto bad = [&](const char* what) {
+        g_err = std::string(who) + ": " + what;
+        return RTG_ERR_ARG;
+    };
+    if (!cam || !proj) return bad("both camera records are required");
+    static_assert(sizeof(rtg_camera) == 37 * sizeof(float) && sizeof(rtg_camera_proj) == 36 * sizeof(float),
+                  "the camera records are plain float arrays");
+    const float* a = (const float*)cam;
+    for (size_t k = 0; k < sizeof(rtg_camera) / sizeof(float); ++k)
+        if (!std::isfinite(a[k])) return bad("a field of the camera record is not finite");
+    const float* b = (const float*)proj;
+    for (size_t k = 0; k < sizeof(rtg_camera_proj) / sizeof(float); ++k)
+        if (!std::isfinite(b[k])) return bad("a field of the projection record is not finite");
+    if (cam->width != (float)h->W || cam->height != (float)h->H) return bad("width and height must equal the handle's");
+    return RTG_OK;
+}
+
 extern "C" {
 
 int32_t rtg_abi_version(void) { return RTG_ABI_VERSION; }
@@ -197,6 +216,7 @@ void rtg_destroy(rtg_handle* h) {
     }
     if (h->entry) (void)hipEventDestroy(h->entry);
     denoise_release(h);
+    temporal_release(h);
     (void)hipFree(h->d_env_table);
     (void)hipFree(h->d_light_table);
     (void)hipFree(h->d_phys);
@@ -223,6 +243,39 @@ int rtg_set_integrator(rtg_handle* h, int integrator) {
     }
     if (int rc = flush_pending(h)) return rc;  // queued calls render with the settings they were queued under
     h->integrator = integrator;
+    return RTG_OK;
+}
+
+int rtg_set_camera(rtg_handle* h, const rtg_camera* cam, const rtg_camera_proj* proj) {
+    if (!h) { g_err = "rtg_set_camera: null handle"; return RTG_ERR_ARG; }
+    if (int rc = camera_check("rtg_set_camera", h, cam, proj)) return rc;
+    HIPOK(hipSetDevice(h->device));
+    if (int rc = join_frames(h)) return rc;  // queued calls render with the camera they were queued under
+    HIPOK(hipStreamSynchronize(h->stream));
+    std::memcpy(h->cam.ip, cam->inv_proj, sizeof(h->cam.ip));  // as prepare_scene takes them from the descriptor
+    std::memcpy(h->cam.cm, cam->camera, sizeof(h->cam.cm));
+    h->cam.ox = cam->origin[0];
+    h->cam.oy = cam->origin[1];
+    h->cam.oz = cam->origin[2];
+    h->cam.width = cam->width;
+    h->cam.height = cam->height;
+    h->proj = *proj;
+    denoise_drop_guides(h);
+    return RTG_OK;
+}
+
+int rtg_get_camera(rtg_handle* h, rtg_camera* cam, rtg_camera_proj* proj) {
+    if (!h) { g_err = "rtg_get_camera: null handle"; return RTG_ERR_ARG; }
+    if (cam) {
+        std::memcpy(cam->inv_proj, h->cam.ip, sizeof(h->cam.ip));
+        std::memcpy(cam->camera, h->cam.cm, sizeof(h->cam.cm));
+        cam->origin[0] = h->cam.ox;
+        cam->origin[1] = h->cam.oy;
+        cam->origin[2] = h->cam.oz;
+        cam->width = h->cam.width;
+        cam->height = h->cam.height;
+    }
+    if (proj) *proj = h->proj;
     return RTG_OK;
 }
 

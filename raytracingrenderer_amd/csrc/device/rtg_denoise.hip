@@ -233,6 +233,10 @@ void denoise_release(rtg_handle* h) {
     h->dn = nullptr;
 }
 
+void denoise_drop_guides(rtg_handle* h) {
+    if (h->dn) h->dn->guides_ready = false;
+}
+
 // the handle's denoiser state, allocated on first use
 static int ensure_state(rtg_handle* h) {
     if (!h->dn) {

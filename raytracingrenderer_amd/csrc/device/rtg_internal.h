@@ -322,6 +322,7 @@ struct ChunkSlot {
 };
 
 struct DenoiseState;  // rtg_denoise.hip
+struct TemporalState;  // rtg_temporal.hip
 
 struct rtg_handle {
     int device = 0;
@@ -395,6 +396,7 @@ struct rtg_handle {
     int cap_cnt = 0;
     std::vector<hipEvent_t> tev;  // [b]: k_trace(b) has finished (a launch that never wrote its counts)
     DenoiseState* dn = nullptr;   // denoiser buffers and cached guides, allocated by the first rtg_denoise*
+    TemporalState* tp = nullptr;  // history, its camera and guide, allocated by the first rtg_temporal_* / rtg_geometry_guide
     // rtg_set_env_sampling (rtg_env.hip): the alias table over the environment map's cells, built by the
     // first RTG_ENV_LUMINANCE setting and kept until rtg_destroy
     int env_mode = RTG_ENV_UNIFORM;
@@ -556,6 +558,12 @@ int denoise_film(rtg_handle* h, const float* d_sum, uint32_t spp, const rtg_deno
 int denoise_check_params(const char* who, const rtg_denoise_params* p);
 // frees the handle's denoiser state (rtg_destroy)
 void denoise_release(rtg_handle* h);
+// the cached guides belong to another camera (rtg_set_camera): the next rtg_denoise renders them again
+void denoise_drop_guides(rtg_handle* h);
+// RTG_ERR_ARG (with "who: ..." as the message) unless both records are given, finite and of the film's size
+int camera_check(const char* who, const rtg_handle* h, const rtg_camera* cam, const rtg_camera_proj* proj);
+// rtg_temporal.hip: frees the handle's temporal state (rtg_destroy, rtg_temporal_reset)
+void temporal_release(rtg_handle* h);
 // rtg_env.hip: the table k_shade_env samples the environment light from under the handle's setting and
 // integrator, or one with a null pointer (uniform sampling: today's k_shade launches)
 EnvTable env_table_of(const rtg_handle* h);

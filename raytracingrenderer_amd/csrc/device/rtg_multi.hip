@@ -535,6 +535,17 @@ int rtg_group_set_material_model(rtg_group* g, int mode) {
     return RTG_OK;
 }
 
+int rtg_group_set_camera(rtg_group* g, const rtg_camera* cam, const rtg_camera_proj* proj) {
+    if (!g || g->h.empty()) { g_err = "rtg_group_set_camera: null group"; return RTG_ERR_ARG; }
+    // checked once for all ranks (they hold films of one size), so an argument error leaves every rank's camera
+    if (int rc = camera_check("rtg_group_set_camera", g->h[0], cam, proj)) return rc;
+    for (rtg_handle* h : g->h) {
+        const int rc = rtg_set_camera(h, cam, proj);
+        if (rc) return rc;
+    }
+    return RTG_OK;
+}
+
 int rtg_group_set_path_mis(rtg_group* g, int mode) {
     if (!g) { g_err = "rtg_group_set_path_mis: null group"; return RTG_ERR_ARG; }
     // checked once for all ranks, so an argument error leaves every rank's setting as it was

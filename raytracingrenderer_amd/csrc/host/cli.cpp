@@ -40,6 +40,9 @@
 // Path-tracer MIS (rtg_set_path_mis): -pathMIS off|power (off: the reference's pathTrace; power: NEE and
 // BSDF-sampled emitter hits combined with the power heuristic, a miss weighted by the throughput), for one
 // device and for -gpus / -devices alike.
+// Camera pose (rtg_set_camera): -from "x y z" -to "x y z" -up "x y z" -fov degrees override scene.json's
+// pose through rth_camera_look_at, the loader's own camera code; each is optional and keeps the scene's
+// value when absent. For one device and for -gpus / -devices alike.
 // Multi-GPU (one node): -gpus N renders on devices 0..N-1, -devices a,b,... on a list. Rank r
 // renders the 32x32 tiles with (tile_x + tile_y) % N == r, and the film is assembled on the first
 // device from every device's own tiles (packed, one RCCL send per device, scattered) before it is
@@ -136,6 +139,30 @@ int main(int argc, char** argv) {
     uint32_t n_params = 0;
     const rtg_material_params* params = trn == "1" ? rth_scene_material_params_transmissive(scene, &n_params)
                                                    : rth_scene_material_params(scene, &n_params);
+    // -from / -to / -up / -fov: the scene's pose with the given parts replaced (rth_camera_look_at)
+    const bool pose_given = args.count("-from") || args.count("-to") || args.count("-up") || args.count("-fov");
+    rtg_camera new_cam{};
+    rtg_camera_proj new_proj{};
+    if (pose_given) {
+        float from[3], to[3], up[3], fov = 0.0f;
+        int32_t flip_x = 0;
+        if (rth_scene_camera_pose(scene, from, to, up, &fov, &flip_x) != 0) return die("camera pose", rth_last_error());
+        auto vec3 = [&](const char* k, float* v) {
+            if (!args.count(k)) return true;
+            std::stringstream ss(args[k]);
+            float t[3];
+            std::string rest;
+            if (!(ss >> t[0] >> t[1] >> t[2]) || (ss >> rest)) return false;
+            v[0] = t[0]; v[1] = t[1]; v[2] = t[2];
+            return true;
+        };
+        if (!vec3("-from", from)) return die("-from", "three numbers, as \"x y z\"");
+        if (!vec3("-to", to)) return die("-to", "three numbers, as \"x y z\"");
+        if (!vec3("-up", up)) return die("-up", "three numbers, as \"x y z\"");
+        if (args.count("-fov")) fov = std::stof(args["-fov"]);
+        if (rth_camera_look_at(from, to, up, fov, info.width, info.height, flip_x, &new_cam, &new_proj) != 0)
+            return die("rth_camera_look_at", rth_last_error());
+    }
     rtg_handle* rt = nullptr;
     rtg_group* grp = nullptr;
     if (devices.empty()) {
@@ -148,6 +175,7 @@ int main(int argc, char** argv) {
                          rtg_set_material_model(rt, RTG_MATERIALS_PHYSICAL) != 0))
             return die("rtg_set_material_model", rtg_last_error());
         if (rtg_set_path_mis(rt, path_mis) != 0) return die("rtg_set_path_mis", rtg_last_error());
+        if (pose_given && rtg_set_camera(rt, &new_cam, &new_proj) != 0) return die("rtg_set_camera", rtg_last_error());
     } else {
         if (rtg_group_create(devices.data(), (int)devices.size(), rth_scene_desc(scene), &grp) != 0)
             return die("rtg_group_create", rtg_last_error());
@@ -159,6 +187,8 @@ int main(int argc, char** argv) {
                          rtg_group_set_material_model(grp, RTG_MATERIALS_PHYSICAL) != 0))
             return die("rtg_group_set_material_model", rtg_last_error());
         if (rtg_group_set_path_mis(grp, path_mis) != 0) return die("rtg_group_set_path_mis", rtg_last_error());
+        if (pose_given && rtg_group_set_camera(grp, &new_cam, &new_proj) != 0)
+            return die("rtg_group_set_camera", rtg_last_error());
         std::printf("%d devices, own-tile film exchange by %s\n", (int)devices.size(),
                     rtg_group_uses_rccl(grp) ? "RCCL (ncclSend/ncclRecv)"
                     : devices.size() == 1    ? "none (one device)"

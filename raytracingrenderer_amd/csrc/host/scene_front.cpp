@@ -71,6 +71,12 @@ struct TexData {
     std::vector<float> rgb{1.0f, 1.0f, 1.0f};  // Texture::loadDefault: 1x1 white
 };
 
+struct CameraPose {  // scene.json's "from", "to", "up", "fov", "flipX"
+    V3 from, to, up;
+    float fov = 45.0f;
+    int flip_x = 0;
+};
+
 struct BuildNode {
     Box bounds;
     int start = 0, end = 0;
@@ -94,6 +100,7 @@ struct rth_scene {
     std::vector<int32_t> lights;
     rtg_scene_desc desc{};
     rth_scene_info info{};
+    rth::CameraPose pose;                // what scene.json said (rth_scene_camera_pose)
 };
 
 namespace rth {
@@ -244,6 +251,45 @@ static double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
+// loadScene's camera (SceneLoader.h:242-260) from a pose: Matrix::perspective(0.001, 10000, aspect, fov),
+// lookAt(from, to, up).invert(), the flipX negation, then Camera::init / updateView (Scene.h:22-41).
+// rth_load_scene and rth_camera_look_at both run this.
+static void camera_records(const CameraPose& pose, int width, int height, rtg_camera* cam, rtg_camera_proj* cp) {
+    M4 P = perspective(0.001f, 10000.0f, (float)width / (float)height, pose.fov);
+    M4 V = look_at(pose.from, pose.to, pose.up).inverted();
+    if (pose.flip_x == 1) P.m[0] = -P.m[0];
+    M4 invP = P.inverted();  // Camera::init
+    std::memcpy(cam->inv_proj, invP.m, sizeof(invP.m));
+    std::memcpy(cam->camera, V.m, sizeof(V.m));
+    V3 origin = V.mul_point(V3(0, 0, 0));  // Camera::updateView
+    cam->origin[0] = origin.x;
+    cam->origin[1] = origin.y;
+    cam->origin[2] = origin.z;
+    cam->width = (float)width;
+    cam->height = (float)height;
+    // projectOntoCamera state: projectionMatrix, cameraToView, viewDirection, Afilm (Scene.h:22-41)
+    std::memcpy(cp->proj, P.m, sizeof(P.m));
+    M4 Vc = V;
+    M4 c2v = Vc.inverted();
+    std::memcpy(cp->camera_to_view, c2v.m, sizeof(c2v.m));
+    // inverseProjectionMatrix.mulPointAndPerspectiveDivide(Vec3(0, 0, 1)) (Core.h:310-320)
+    const float* m = invP.m;
+    const float vx = 0.0f, vy = 0.0f, vz = 1.0f;
+    V3 v1(((vx * m[0] + vy * m[1]) + vz * m[2]) + m[3], ((vx * m[4] + vy * m[5]) + vz * m[6]) + m[7],
+          ((vx * m[8] + vy * m[9]) + vz * m[10]) + m[11]);
+    float w = ((m[12] * vx) + (m[13] * vy) + (m[14] * vz)) + m[15];
+    w = 1.0f / w;
+    V3 vd(v1.x * w, v1.y * w, v1.z * w);
+    vd = V.mul_vec(vd).normalize();
+    cp->view_direction[0] = vd.x;
+    cp->view_direction[1] = vd.y;
+    cp->view_direction[2] = vd.z;
+    const float wlens = 2.0f / P.m[5];
+    const float aspect = P.m[0] / P.m[5];
+    const float hlens = wlens * aspect;
+    cp->a_film = wlens * hlens;
+}
+
 static bool load_scene(const std::string& dir, const rth_load_options& o, rth_scene* s) {
     auto t0 = std::chrono::steady_clock::now();
     SceneFile sf;
@@ -252,46 +298,13 @@ static bool load_scene(const std::string& dir, const rth_load_options& o, rth_sc
     int height = sf.properties.find("height").as_int(1080);
     if (o.width > 0) width = o.width;
     if (o.height > 0) height = o.height;
-    float fov = sf.properties.find("fov").as_float(45.0f);
-    M4 P = perspective(0.001f, 10000.0f, (float)width / (float)height, fov);
-    V3 from, to, up;
-    sf.properties.find("from").as_vec3(from.x, from.y, from.z);
-    sf.properties.find("to").as_vec3(to.x, to.y, to.z);
-    sf.properties.find("up").as_vec3(up.x, up.y, up.z);
-    M4 V = look_at(from, to, up).inverted();
-    if (sf.properties.find("flipX").as_int(0) == 1) P.m[0] = -P.m[0];
-    M4 invP = P.inverted();  // Camera::init
-    std::memcpy(s->desc.camera.inv_proj, invP.m, sizeof(invP.m));
-    std::memcpy(s->desc.camera.camera, V.m, sizeof(V.m));
-    V3 origin = V.mul_point(V3(0, 0, 0));  // Camera::updateView
-    s->desc.camera.origin[0] = origin.x;
-    s->desc.camera.origin[1] = origin.y;
-    s->desc.camera.origin[2] = origin.z;
-    s->desc.camera.width = (float)width;
-    s->desc.camera.height = (float)height;
-    {  // projectOntoCamera state: projectionMatrix, cameraToView, viewDirection, Afilm (Scene.h:22-41)
-        rtg_camera_proj& cp = s->desc.projection;
-        std::memcpy(cp.proj, P.m, sizeof(P.m));
-        M4 Vc = V;
-        M4 c2v = Vc.inverted();
-        std::memcpy(cp.camera_to_view, c2v.m, sizeof(c2v.m));
-        // inverseProjectionMatrix.mulPointAndPerspectiveDivide(Vec3(0, 0, 1)) (Core.h:310-320)
-        const float* m = invP.m;
-        const float vx = 0.0f, vy = 0.0f, vz = 1.0f;
-        V3 v1(((vx * m[0] + vy * m[1]) + vz * m[2]) + m[3], ((vx * m[4] + vy * m[5]) + vz * m[6]) + m[7],
-              ((vx * m[8] + vy * m[9]) + vz * m[10]) + m[11]);
-        float w = ((m[12] * vx) + (m[13] * vy) + (m[14] * vz)) + m[15];
-        w = 1.0f / w;
-        V3 vd(v1.x * w, v1.y * w, v1.z * w);
-        vd = V.mul_vec(vd).normalize();
-        cp.view_direction[0] = vd.x;
-        cp.view_direction[1] = vd.y;
-        cp.view_direction[2] = vd.z;
-        const float wlens = 2.0f / P.m[5];
-        const float aspect = P.m[0] / P.m[5];
-        const float hlens = wlens * aspect;
-        cp.a_film = wlens * hlens;
-    }
+    CameraPose& pose = s->pose;
+    pose.fov = sf.properties.find("fov").as_float(45.0f);
+    sf.properties.find("from").as_vec3(pose.from.x, pose.from.y, pose.from.z);
+    sf.properties.find("to").as_vec3(pose.to.x, pose.to.y, pose.to.z);
+    sf.properties.find("up").as_vec3(pose.up.x, pose.up.y, pose.up.z);
+    pose.flip_x = sf.properties.find("flipX").as_int(0) == 1 ? 1 : 0;
+    camera_records(pose, width, height, &s->desc.camera, &s->desc.projection);
     s->info.width = width;
     s->info.height = height;
 
@@ -573,6 +586,49 @@ const rtg_material_params* rth_scene_material_params(const rth_scene* s, uint32_
 const rtg_material_params* rth_scene_material_params_transmissive(const rth_scene* s, uint32_t* n) {
     if (n) *n = s ? (uint32_t)s->mat_params_trans.size() : 0u;
     return s ? s->mat_params_trans.data() : nullptr;
+}
+
+int rth_scene_camera_pose(const rth_scene* s, float from[3], float to[3], float up[3], float* fov, int32_t* flip_x) {
+    if (!s) { g_err = "rth_scene_camera_pose: null scene"; return RTG_ERR_ARG; }
+    for (int k = 0; k < 3; ++k) {
+        if (from) from[k] = s->pose.from[k];
+        if (to) to[k] = s->pose.to[k];
+        if (up) up[k] = s->pose.up[k];
+    }
+    if (fov) *fov = s->pose.fov;
+    if (flip_x) *flip_x = s->pose.flip_x;
+    return RTG_OK;
+}
+
+int rth_camera_look_at(const float from[3], const float to[3], const float up[3], float fov_degrees, int32_t width,
+                       int32_t height, int32_t flip_x, rtg_camera* cam, rtg_camera_proj* proj) {
+    auto bad = [](const char* what) {
+        g_err = std::string("rth_camera_look_at: ") + what;
+        return RTG_ERR_ARG;
+    };
+    if (!from || !to || !up || !cam || !proj) return bad("null argument");
+    if (width <= 0 || height <= 0) return bad("width and height must be positive");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(from[k]) || !std::isfinite(to[k]) || !std::isfinite(up[k]))
+            return bad("from, to and up must be finite");
+    if (!std::isfinite(fov_degrees)) return bad("fov must be finite");
+    CameraPose pose;
+    pose.from = V3(from[0], from[1], from[2]);
+    pose.to = V3(to[0], to[1], to[2]);
+    pose.up = V3(up[0], up[1], up[2]);
+    pose.fov = fov_degrees;
+    pose.flip_x = flip_x == 1 ? 1 : 0;
+    const V3 view = pose.from - pose.to;
+    if (!(view.lengthSq() > 0.0f) || !std::isfinite(view.lengthSq())) return bad("from equals to");
+    // Matrix::lookAt normalises up x dir: a zero (or overflowed) cross product has no direction
+    const V3 left = pose.up.cross(view.normalize());
+    if (!(left.lengthSq() > 0.0f) || !std::isfinite(left.lengthSq())) return bad("up is parallel to the view direction");
+    rtg_camera c{};
+    rtg_camera_proj p{};
+    camera_records(pose, width, height, &c, &p);
+    *cam = c;
+    *proj = p;
+    return RTG_OK;
 }
 
 int rth_scene_permutation(const rth_scene* s, uint32_t* out) {

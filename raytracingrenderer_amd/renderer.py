@@ -111,6 +111,16 @@ class Scene:
                 "camera": np.array(c.camera[:], np.float32).reshape(4, 4),
                 "origin": np.array(c.origin[:], np.float32), "width": c.width, "height": c.height}
 
+    @property
+    def camera_pose(self):
+        """What scene.json said: {"from_", "to", "up" (3 floats each), "fov" (degrees), "flip_x"}
+        (rth_scene_camera_pose). look_at(width=w, height=h, **pose) rebuilds desc.camera / desc.projection."""
+        f, t, u = (np.zeros(3, np.float32) for _ in range(3))
+        fov, flip = C.c_float(), C.c_int32()
+        _check(N.rth().rth_scene_camera_pose(self._h, N.ptr(f, C.c_float), N.ptr(t, C.c_float), N.ptr(u, C.c_float),
+                                             C.byref(fov), C.byref(flip)), N.rth().rth_last_error)
+        return {"from_": f, "to": t, "up": u, "fov": fov.value, "flip_x": flip.value}
+
     def permutation(self):
         out = np.zeros(self.desc.n_tris, np.uint32)
         _check(N.rth().rth_scene_permutation(self._h, N.ptr(out, C.c_uint32)), N.rth().rth_last_error)
@@ -124,6 +134,36 @@ def loadScene(scene_dir, width=0, height=0, skip_missing=False, envmap=None, bvh
     h = C.c_void_p()
     _check(N.rth().rth_load_scene(os.fsencode(scene_dir), C.byref(opts), C.byref(h)), N.rth().rth_last_error)
     return Scene(h)
+
+
+def look_at(from_, to, up, fov, width, height, flip_x=0):
+    """The camera records of a pose, (rtg_camera, rtg_camera_proj), built by the loader's own code
+    (rth_camera_look_at): what RayTracer.set_camera takes. Non-finite input, from_ == to, up parallel to
+    the view or a non-positive size raises NativeError."""
+    v = [np.ascontiguousarray(a, np.float32).reshape(-1) for a in (from_, to, up)]
+    if any(len(a) != 3 for a in v):
+        raise ValueError("look_at: from_, to and up take three floats each")
+    cam, proj = N.rtg_camera(), N.rtg_camera_proj()
+    _check(N.rth().rth_camera_look_at(N.ptr(v[0], C.c_float), N.ptr(v[1], C.c_float), N.ptr(v[2], C.c_float),
+                                      float(fov), int(width), int(height), int(flip_x), C.byref(cam), C.byref(proj)),
+           N.rth().rth_last_error)
+    return cam, proj
+
+
+def _temporal_params(max_history, plane_tolerance, normal_cos):
+    return N.rtg_temporal_params(float(max_history), float(plane_tolerance), float(normal_cos))
+
+
+def temporal_check(max_history=64.0, plane_tolerance=0.01, normal_cos=0.9):
+    """rtg_temporal_check: the argument check of RayTracer.temporal alone (no device needed)."""
+    p = _temporal_params(max_history, plane_tolerance, normal_cos)
+    _check(N.rtg().rtg_temporal_check(C.byref(p)), N.rtg().rtg_last_error)
+
+
+def temporal_defaults():
+    p = N.rtg_temporal_params()
+    _check(N.rtg().rtg_temporal_defaults(C.byref(p)), N.rtg().rtg_last_error)
+    return {"max_history": p.max_history, "plane_tolerance": p.plane_tolerance, "normal_cos": p.normal_cos}
 
 
 def write_synthetic_scene(out_dir, n_tris=1_000_000, seed=20251015, width=1024, height=1024):
@@ -408,6 +448,68 @@ class RayTracer:
         mode = self.INTEGRATORS[integrator] if isinstance(integrator, str) else int(integrator)
         _check(self._lib.rtg_set_integrator(self._h, mode), self._lib.rtg_last_error)
         self.integrator = integrator
+
+    def set_camera(self, camera, projection):
+        """Replace the camera of the live tracer (rtg_set_camera): an rtg_camera and an rtg_camera_proj,
+        e.g. from look_at(). Frames queued earlier keep the camera they were queued under; the film and
+        SPP are left alone (clear() them, as Main.cpp does after a move); the denoiser's guides are
+        rendered again by the next denoise(). The film size cannot change."""
+        _check(self._lib.rtg_set_camera(self._h, C.byref(camera), C.byref(projection)), self._lib.rtg_last_error)
+
+    def look_at(self, from_, to, up, fov=None):
+        """set_camera(*look_at(...)) at this tracer's film size, with the scene's flipX and, for fov None,
+        the scene's fov."""
+        pose = self.scene.camera_pose
+        self.set_camera(*look_at(from_, to, up, pose["fov"] if fov is None else fov, self.width, self.height,
+                                 pose["flip_x"]))
+
+    def camera(self):
+        """(rtg_camera, rtg_camera_proj): the records in use (rtg_get_camera)."""
+        cam, proj = N.rtg_camera(), N.rtg_camera_proj()
+        _check(self._lib.rtg_get_camera(self._h, C.byref(cam), C.byref(proj)), self._lib.rtg_last_error)
+        return cam, proj
+
+    def geometry_guide(self):
+        """(pos_t, normal_id), (H, W, 4) float32 each: per pixel the first hit of the pinhole ray through
+        its centre, {X.xyz, t} and {unit geometric normal, triangle id as bits}; a miss is {0, 0, 0,
+        FLT_MAX} {0, 0, 0, -1} (rtg_geometry_guide). normal_id[..., 3].view(np.int32) gives the ids."""
+        a = np.zeros((self.height, self.width, 4), np.float32)
+        b = np.zeros((self.height, self.width, 4), np.float32)
+        _check(self._lib.rtg_geometry_guide(self._h, N.ptr(a, C.c_float), N.ptr(b, C.c_float)),
+               self._lib.rtg_last_error)
+        return a, b
+
+    def temporal(self, max_history=64.0, plane_tolerance=0.01, normal_cos=0.9):
+        """Temporal accumulation by reprojection (rtg_temporal_accumulate): film / SPP blended into a
+        per-pixel history that follows set_camera() through the scene's geometry. The loop is: move,
+        clear(), render(), temporal(). Returns the (H, W, 3) float32 image; the film, SPP and the settings
+        stay as they were. Waits for queued frames first."""
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        p = _temporal_params(max_history, plane_tolerance, normal_cos)
+        _check(self._lib.rtg_temporal_accumulate(self._h, C.byref(p), N.ptr(out, C.c_float)),
+               self._lib.rtg_last_error)
+        return out
+
+    def temporal_history(self):
+        """The history, (H, W, 4) float32: rgb and the effective sample count len."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        _check(self._lib.rtg_temporal_history(self._h, N.ptr(out, C.c_float)), self._lib.rtg_last_error)
+        return out
+
+    def temporal_reset(self):
+        """Drop the history, its camera and the cached guides (rtg_temporal_reset)."""
+        _check(self._lib.rtg_temporal_reset(self._h), self._lib.rtg_last_error)
+
+    def copy_temporal_to(self, device_ptr):
+        """The last temporal() result, (H, W, 3) float32, copied to device memory on this GPU."""
+        _check(self._lib.rtg_temporal_copy_device(self._h, C.c_void_p(device_ptr)), self._lib.rtg_last_error)
+
+    def temporal_ms(self):
+        """(guide_ms, accumulate_ms): device time of the last call's guide pass (0 when none ran) and of
+        its k_temporal launch."""
+        g, a = C.c_double(), C.c_double()
+        _check(self._lib.rtg_temporal_ms(self._h, C.byref(g), C.byref(a)), self._lib.rtg_last_error)
+        return g.value, a.value
 
     def set_camera_sampling(self, filter="none", filter_radius=None, lens_radius=0.0, focal_distance=1.0):
         """Anti-aliasing and depth of field (rtg_set_camera_sampling). filter "none" (default: every
@@ -823,6 +925,10 @@ class RayTracerGroup:
         """RayTracer.set_camera_sampling on every rank (rtg_group_set_camera_sampling)."""
         p = _camera_sampling(filter, filter_radius, lens_radius, focal_distance)
         _check(self._lib.rtg_group_set_camera_sampling(self._g, C.byref(p)), self._lib.rtg_last_error)
+
+    def set_camera(self, camera, projection):
+        """RayTracer.set_camera on every rank (rtg_group_set_camera)."""
+        _check(self._lib.rtg_group_set_camera(self._g, C.byref(camera), C.byref(projection)), self._lib.rtg_last_error)
 
     def set_env_sampling(self, mode="uniform"):
         """RayTracer.set_env_sampling on every rank (rtg_group_set_env_sampling)."""

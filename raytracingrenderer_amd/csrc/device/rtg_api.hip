@@ -85,25 +85,26 @@ int upload_scene(int device, const HostScene& hs, rtg_handle* h) {
     h->rebuilt = hs.rebuilt;
     h->usew = hs.usew;
     int rc;
-    if ((rc = dev_upload(&h->d_nodes, hs.nodes))) return rc;
-    if ((rc = dev_upload(&h->d_nodesq, hs.nodesq))) return rc;
-    if ((rc = dev_upload(&h->d_leafbox, hs.leafbox))) return rc;
-    if (!hs.img.empty() && (rc = dev_upload(&h->d_img, hs.img))) return rc;
-    if ((rc = dev_upload(&h->d_tris48, hs.tris48))) return rc;
-    if ((rc = dev_upload(&h->d_shade, hs.shade))) return rc;
-    if ((rc = dev_upload(&h->d_mats, hs.mats))) return rc;
-    if ((rc = dev_upload(&h->d_lights, hs.lights))) return rc;
-    if ((rc = dev_upload(&h->d_texinfo, hs.texinfo))) return rc;
-    if ((rc = dev_upload(&h->d_texels, hs.texels))) return rc;
+    SceneBufs& d = h->scene;
+    if ((rc = d.nodes.upload(hs.nodes))) return rc;
+    if ((rc = d.nodesq.upload(hs.nodesq))) return rc;
+    if ((rc = d.leafbox.upload(hs.leafbox))) return rc;
+    if (!hs.img.empty() && (rc = d.img.upload(hs.img))) return rc;
+    if ((rc = d.tris48.upload(hs.tris48))) return rc;
+    if ((rc = d.shade.upload(hs.shade))) return rc;
+    if ((rc = d.mats.upload(hs.mats))) return rc;
+    if ((rc = d.lights.upload(hs.lights))) return rc;
+    if ((rc = d.texinfo.upload(hs.texinfo))) return rc;
+    if ((rc = d.texels.upload(hs.texels))) return rc;
 
     SceneView& s = h->sv;
-    s.nodes = h->d_nodes;
-    s.tris48 = h->d_tris48;
-    s.shade = h->d_shade;
-    s.mats = h->d_mats;
-    s.lights = h->d_lights;
-    s.texinfo = h->d_texinfo;
-    s.texels = (const float4*)h->d_texels;
+    s.nodes = d.nodes.p;
+    s.tris48 = d.tris48.p;
+    s.shade = d.shade.p;
+    s.mats = d.mats.p;
+    s.lights = d.lights.p;
+    s.texinfo = d.texinfo.p;
+    s.texels = (const float4*)d.texels.p;
     s.n_mats = (int)hs.mats.size();
     s.n_lights = hs.n_lights;
     s.pmf = 1.f / (float)hs.n_lights;  // Scene::sampleLight (Scene.h:137-138), the same IEEE division
@@ -114,11 +115,11 @@ int upload_scene(int device, const HostScene& hs, rtg_handle* h) {
     s.env_uniform = hs.env_uniform ? 1 : 0;
     for (int k = 0; k < 3; ++k) s.env_one[k] = hs.env_one[k];
     s.root_word = hs.root_word;
-    s.nodesq = h->d_nodesq;
-    s.leafbox = h->d_leafbox;
+    s.nodesq = d.nodesq.p;
+    s.leafbox = d.leafbox.p;
     s.root_wordw = hs.root_wordw;
     s.usew = hs.usew ? 1 : 0;
-    s.img = hs.img.empty() ? nullptr : h->d_img;
+    s.img = d.img.p;
     s.img_n4 = (int)hs.img.size();
     s.img_tri = hs.img_tri;
     s.img_lb = hs.img_lb;
@@ -217,15 +218,9 @@ void rtg_destroy(rtg_handle* h) {
     if (h->entry) (void)hipEventDestroy(h->entry);
     denoise_release(h);
     temporal_release(h);
-    (void)hipFree(h->d_env_table);
-    (void)hipFree(h->d_light_table);
-    (void)hipFree(h->d_phys);
-    (void)hipFree(h->d_phys_index);
-    (void)hipFree(h->d_mis_index);
-    (void)hipFree(h->d_mis_ref);
-    (void)hipFree(h->d_img);
-    (void)hipFree(h->d_nodes); (void)hipFree(h->d_nodesq); (void)hipFree(h->d_leafbox); (void)hipFree(h->d_tris48); (void)hipFree(h->d_shade); (void)hipFree(h->d_mats);
-    (void)hipFree(h->d_lights); (void)hipFree(h->d_texinfo); (void)hipFree(h->d_texels); (void)hipFree(h->d_film);
+    h->mt = ModeTables{};  // here, not in `delete h`: the device is the handle's and its streams still exist
+    h->scene = SceneBufs{};
+    (void)hipFree(h->d_film);
     (void)hipFree(h->d_pix); (void)hipFree(h->d_qctr); (void)hipFree(h->d_stats);
     for (auto& e : h->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : h->kev) (void)hipEventDestroy(e);
@@ -249,9 +244,7 @@ int rtg_set_integrator(rtg_handle* h, int integrator) {
 int rtg_set_camera(rtg_handle* h, const rtg_camera* cam, const rtg_camera_proj* proj) {
     if (!h) { g_err = "rtg_set_camera: null handle"; return RTG_ERR_ARG; }
     if (int rc = camera_check("rtg_set_camera", h, cam, proj)) return rc;
-    HIPOK(hipSetDevice(h->device));
-    if (int rc = join_frames(h)) return rc;  // queued calls render with the camera they were queued under
-    HIPOK(hipStreamSynchronize(h->stream));
+    if (int rc = settle(h)) return rc;
     std::memcpy(h->cam.ip, cam->inv_proj, sizeof(h->cam.ip));  // as prepare_scene takes them from the descriptor
     std::memcpy(h->cam.cm, cam->camera, sizeof(h->cam.cm));
     h->cam.ox = cam->origin[0];
@@ -296,9 +289,7 @@ int rtg_set_options(rtg_handle* h, int max_depth, int cull, uint32_t max_paths) 
 
 int rtg_synchronize(rtg_handle* h) {
     if (!h) return RTG_ERR_ARG;
-    HIPOK(hipSetDevice(h->device));
-    if (int rc = join_frames(h)) return rc;
-    HIPOK(hipStreamSynchronize(h->stream));
+    if (int rc = settle(h)) return rc;
     float ms = 0;
     if (hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess) h->stats.render_ms = ms;
     return RTG_OK;
@@ -329,9 +320,7 @@ int rtg_film_copy_device(rtg_handle* h, void* dst) {
 
 int rtg_film_load(rtg_handle* h, const float* rgb, uint32_t spp) {
     if (!h || !rgb) return RTG_ERR_ARG;
-    HIPOK(hipSetDevice(h->device));
-    if (int rc = join_frames(h)) return rc;
-    HIPOK(hipStreamSynchronize(h->stream));  // (hipMemcpy does not order against non-blocking streams)
+    if (int rc = settle(h)) return rc;
     HIPOK(hipMemcpy(h->d_film, rgb, (size_t)h->W * h->H * 3 * sizeof(float), hipMemcpyHostToDevice));
     h->spp = spp;
     return RTG_OK;
@@ -352,9 +341,7 @@ int rtg_clear(rtg_handle* h) {
 
 int rtg_get_stats(rtg_handle* h, rtg_stats* out) {
     if (!h || !out) return RTG_ERR_ARG;
-    HIPOK(hipSetDevice(h->device));
-    if (int rc = join_frames(h)) return rc;
-    HIPOK(hipStreamSynchronize(h->stream));
+    if (int rc = settle(h)) return rc;
     unsigned long long c[RTG_NSTATS] = {};
     HIPOK(hipMemcpy(c, h->d_stats, sizeof(c), hipMemcpyDeviceToHost));
     h->stats.node_visits = c[0];
@@ -384,17 +371,10 @@ int rtg_get_stats(rtg_handle* h, rtg_stats* out) {
 int rtg_probe_bsdf(const float* cases, uint32_t n, float* out) {
     if (!cases || !out) return RTG_ERR_ARG;
     if (n == 0) return RTG_OK;
-    float *d_in = nullptr, *d_out = nullptr;
-    HIPOK(hipMalloc((void**)&d_in, (size_t)n * 20 * sizeof(float)));
-    HIPOK(hipMalloc((void**)&d_out, (size_t)n * 11 * sizeof(float)));
-    HIPOK(hipMemcpy(d_in, cases, (size_t)n * 20 * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_probe_bsdf, dim3((n + 255) / 256), dim3(256), 0, nullptr, d_in, (int)n, d_out);
-    HIPOK(hipGetLastError());
-    HIPOK(hipDeviceSynchronize());
-    HIPOK(hipMemcpy(out, d_out, (size_t)n * 11 * sizeof(float), hipMemcpyDeviceToHost));
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return RTG_OK;
+    return probe_run({{cases, (size_t)n * 20 * sizeof(float)}}, {{out, (size_t)n * 11 * sizeof(float)}}, [&](void* const* d) {
+        hipLaunchKernelGGL(k_probe_bsdf, dim3((n + 255) / 256), dim3(256), 0, nullptr, (const float*)d[0], (int)n,
+                           (float*)d[1]);
+    });
 }
 
 int rtg_probe_texture(int mode, const float* texels_rgb, uint32_t w, uint32_t h, const float* in, uint32_t n,
@@ -423,42 +403,22 @@ int rtg_probe_texture(int mode, const float* texels_rgb, uint32_t w, uint32_t h,
         t4[4 * j + 3] = 0.0f;
     }
     const size_t nin = (size_t)n * (env ? 3 : 2), nout = (size_t)n * 3;
-    float *d_tex = nullptr, *d_in = nullptr, *d_out = nullptr;
-    auto run = [&]() -> int {
-        HIPOK(hipMalloc((void**)&d_tex, t4.size() * sizeof(float)));
-        HIPOK(hipMalloc((void**)&d_in, nin * sizeof(float)));
-        HIPOK(hipMalloc((void**)&d_out, nout * sizeof(float)));
-        HIPOK(hipMemcpy(d_tex, t4.data(), t4.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIPOK(hipMemcpy(d_in, in, nin * sizeof(float), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_probe_texture, dim3((n + 255) / 256), dim3(256), 0, nullptr, env ? 1 : 0, uni ? 1 : 0,
-                           (const float4*)d_tex, (int)w, (int)h, (const float*)d_in, (int)n, d_out);
-        HIPOK(hipGetLastError());
-        HIPOK(hipDeviceSynchronize());
-        HIPOK(hipMemcpy(out, d_out, nout * sizeof(float), hipMemcpyDeviceToHost));
-        return RTG_OK;
-    };
-    const int rc = run();
-    (void)hipFree(d_tex);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return rc;
+    return probe_run({{t4.data(), t4.size() * sizeof(float)}, {in, nin * sizeof(float)}}, {{out, nout * sizeof(float)}},
+                     [&](void* const* d) {
+                         hipLaunchKernelGGL(k_probe_texture, dim3((n + 255) / 256), dim3(256), 0, nullptr, env ? 1 : 0,
+                                            uni ? 1 : 0, (const float4*)d[0], (int)w, (int)h, (const float*)d[1], (int)n,
+                                            (float*)d[2]);
+                     });
 }
 
 int rtg_probe_math(int fn, const float* in, uint32_t n, float* out) {
     if (!in || !out || fn < 0 || fn > 4 || n > 0x7fffffffu) return RTG_ERR_ARG;
     if (n == 0) return RTG_OK;
     const size_t nin = (size_t)n * (fn == 4 ? 2 : 1), nout = (size_t)n * (fn == 2 ? 2 : 1);
-    float *d_in = nullptr, *d_out = nullptr;
-    HIPOK(hipMalloc((void**)&d_in, nin * sizeof(float)));
-    HIPOK(hipMalloc((void**)&d_out, nout * sizeof(float)));
-    HIPOK(hipMemcpy(d_in, in, nin * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_probe_math, dim3((n + 255) / 256), dim3(256), 0, nullptr, fn, d_in, (int)n, d_out);
-    HIPOK(hipGetLastError());
-    HIPOK(hipDeviceSynchronize());
-    HIPOK(hipMemcpy(out, d_out, nout * sizeof(float), hipMemcpyDeviceToHost));
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return RTG_OK;
+    return probe_run({{in, nin * sizeof(float)}}, {{out, nout * sizeof(float)}}, [&](void* const* d) {
+        hipLaunchKernelGGL(k_probe_math, dim3((n + 255) / 256), dim3(256), 0, nullptr, fn, (const float*)d[0], (int)n,
+                           (float*)d[1]);
+    });
 }
 
 }  // extern "C"

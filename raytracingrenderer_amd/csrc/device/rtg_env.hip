@@ -39,41 +39,28 @@ __global__ void k_probe_env(EnvTable et, const unsigned* r0, const float* d, uns
     o[0] = wi.x; o[1] = wi.y; o[2] = wi.z; o[3] = pdf;
 }
 
-static bool env_active(const rtg_handle* h) { return h->env_mode == RTG_ENV_LUMINANCE && h->d_env_table != nullptr; }
-
-EnvTable env_table_of(const rtg_handle* h) {
-    const bool samples_light = h->integrator == RTG_INTEGRATOR_PATH || h->integrator == RTG_INTEGRATOR_DIRECT ||
-                               h->integrator == RTG_INTEGRATOR_DIRECT_MIS;
-    if (!env_active(h) || !samples_light) return EnvTable{nullptr, 0u, 0u, 0u};
-    const unsigned w = (unsigned)h->sv.env_w, hh = (unsigned)h->sv.env_h;
-    return EnvTable{h->d_env_table, w * hh, w, hh};
-}
+static bool env_active(const rtg_handle* h) { return env_table_set(h).table != nullptr; }
 
 // The map's w * h cell weights (include/rtg.h): the footprint maxima from the texels on the device,
 // times the row's sin theta on the host. Waits for the handle's stream.
 int env_cell_weights(rtg_handle* h, std::vector<double>& wts) {
     const int w = h->sv.env_w, hh = h->sv.env_h;
     const uint32_t n = (uint32_t)w * (uint32_t)hh;
-    float* d_max = nullptr;
+    DevBuf<float> d_max;
     std::vector<float> maxlum(n);
     wts.assign(n, 0.0);
-    auto run = [&]() -> int {
-        HIPOK(hipMalloc((void**)&d_max, (size_t)n * sizeof(float)));
-        (void)hipGetLastError();  // drop any stale error left by other code on this thread (as render_impl does)
-        hipLaunchKernelGGL(k_env_weights, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->sv.texels + h->sv.env_off, w,
-                           hh, d_max);
-        LAUNCH_OK("k_env_weights");
-        HIPOK(hipMemcpyAsync(maxlum.data(), d_max, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIPOK(hipStreamSynchronize(h->stream));
-        for (int cy = 0; cy < hh; ++cy) {
-            const double rs = std::sin(3.14159265358979323846 * ((double)cy + 0.5) / (double)hh);
-            for (int cx = 0; cx < w; ++cx) wts[(size_t)cy * w + cx] = (double)maxlum[(size_t)cy * w + cx] * rs;
-        }
-        return RTG_OK;
-    };
-    const int rc = run();
-    (void)hipFree(d_max);
-    return rc;
+    if (int rc = d_max.alloc(n)) return rc;
+    (void)hipGetLastError();  // drop any stale error left by other code on this thread (as render_impl does)
+    hipLaunchKernelGGL(k_env_weights, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->sv.texels + h->sv.env_off, w, hh,
+                       d_max.p);
+    LAUNCH_OK("k_env_weights");
+    HIPOK(hipMemcpyAsync(maxlum.data(), d_max.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPOK(hipStreamSynchronize(h->stream));
+    for (int cy = 0; cy < hh; ++cy) {
+        const double rs = std::sin(3.14159265358979323846 * ((double)cy + 0.5) / (double)hh);
+        for (int cx = 0; cx < w; ++cx) wts[(size_t)cy * w + cx] = (double)maxlum[(size_t)cy * w + cx] * rs;
+    }
+    return RTG_OK;
 }
 
 // The handle's table, once: weights on the device, Vose on the host, entries uploaded. A black map
@@ -81,28 +68,18 @@ int env_cell_weights(rtg_handle* h, std::vector<double>& wts) {
 static int build_env_table(rtg_handle* h) {
     const auto t0 = std::chrono::steady_clock::now();
     const uint32_t n = (uint32_t)h->sv.env_w * (uint32_t)h->sv.env_h;
-    uint4* d_tab = nullptr;
+    DevBuf<uint4> d_tab;
     std::vector<uint32_t> entries;
     std::vector<double> wts;
-    bool have = false;
-    auto run = [&]() -> int {
-        if (int rc = env_cell_weights(h, wts)) return rc;
-        rtg_env::Alias al;
-        have = rtg_env::build_alias(wts.data(), n, al);
-        if (!have) return RTG_OK;
+    if (int rc = env_cell_weights(h, wts)) return rc;
+    rtg_env::Alias al;
+    if (rtg_env::build_alias(wts.data(), n, al)) {
         entries.resize((size_t)n * 4);
         rtg_env::pack_entries(al, entries.data());
-        HIPOK(hipMalloc((void**)&d_tab, (size_t)n * 16));
-        HIPOK(hipMemcpy(d_tab, entries.data(), (size_t)n * 16, hipMemcpyHostToDevice));
-        return RTG_OK;
-    };
-    const int rc = run();
-    if (rc != RTG_OK) {
-        (void)hipFree(d_tab);
-        return rc;
+        if (int rc = d_tab.upload((const uint4*)entries.data(), n)) return rc;
     }
     h->env_built = true;
-    h->d_env_table = have ? d_tab : nullptr;
+    h->mt.env = std::move(d_tab);
     h->env_entries.swap(entries);
     h->env_weights.swap(wts);
     h->env_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -128,9 +105,7 @@ int rtg_set_env_sampling(rtg_handle* h, int mode) {
     const bool lit = h->env_light && h->sv.env_tex >= 0;  // else nothing to sample: accepted, stays uniform
     if (int rc = rtg_env_sampling_check(mode, lit ? (uint32_t)h->sv.env_w : 0u, lit ? (uint32_t)h->sv.env_h : 0u))
         return rc;
-    HIPOK(hipSetDevice(h->device));
-    if (int rc = join_frames(h)) return rc;  // queued calls render with the settings they were queued under
-    HIPOK(hipStreamSynchronize(h->stream));
+    if (int rc = settle(h)) return rc;
     if (mode == RTG_ENV_LUMINANCE && lit && !h->env_built)
         if (int rc = build_env_table(h)) return rc;
     h->env_mode = mode;
@@ -182,29 +157,11 @@ int rtg_probe_env_samples(rtg_handle* h, const uint32_t* r0, const float* d, uin
     if (n > 0x7fffffffu / 4u) { g_err = "rtg_probe_env_samples: too many cases"; return RTG_ERR_ARG; }
     if (n == 0) return RTG_OK;
     HIPOK(hipSetDevice(h->device));
-    const unsigned w = (unsigned)h->sv.env_w, hh = (unsigned)h->sv.env_h;
-    const EnvTable et{h->d_env_table, w * hh, w, hh};
-    unsigned* d_r = nullptr;
-    float *d_d = nullptr, *d_out = nullptr;
-    auto run = [&]() -> int {
-        HIPOK(hipMalloc((void**)&d_r, (size_t)n * sizeof(unsigned)));
-        HIPOK(hipMalloc((void**)&d_d, (size_t)n * 3 * sizeof(float)));
-        HIPOK(hipMalloc((void**)&d_out, (size_t)n * 4 * sizeof(float)));
-        HIPOK(hipMemcpy(d_r, r0, (size_t)n * sizeof(unsigned), hipMemcpyHostToDevice));
-        HIPOK(hipMemcpy(d_d, d, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
-        (void)hipGetLastError();  // (a stale error of other code on this thread is not this launch's)
-        hipLaunchKernelGGL(k_probe_env, dim3((n + 255) / 256), dim3(256), 0, nullptr, et, (const unsigned*)d_r,
-                           (const float*)d_d, (unsigned)n, d_out);
-        HIPOK(hipGetLastError());
-        HIPOK(hipDeviceSynchronize());
-        HIPOK(hipMemcpy(out, d_out, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost));
-        return RTG_OK;
-    };
-    const int rc = run();
-    (void)hipFree(d_r);
-    (void)hipFree(d_d);
-    (void)hipFree(d_out);
-    return rc;
+    return probe_run({{r0, (size_t)n * sizeof(unsigned)}, {d, (size_t)n * 3 * sizeof(float)}},
+                     {{out, (size_t)n * 4 * sizeof(float)}}, [&](void* const* p) {
+                         hipLaunchKernelGGL(k_probe_env, dim3((n + 255) / 256), dim3(256), 0, nullptr, env_table_set(h),
+                                            (const unsigned*)p[0], (const float*)p[1], (unsigned)n, (float*)p[2]);
+                     });
 }
 
 }  // extern "C"

@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <rocprofiler-sdk-roctx/roctx.h>
 
+#include <algorithm>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -280,12 +282,73 @@ struct RoctxRange {
         }                                                                                    \
     } while (0)
 
+// A device allocation of n records of T and its one owner: move-only, freed by the destructor (on the
+// device that is current then: its holders call hipSetDevice first). alloc and upload replace what it
+// held; a builder fills a local one and move-assigns it into the handle once everything has succeeded,
+// so a failure leaves the handle's table as it was.
 template <class T>
-static int dev_upload(T** dst, const std::vector<T>& src) {
-    *dst = nullptr;
-    size_t bytes = std::max<size_t>(src.size(), 1) * sizeof(T);
-    HIPOK(hipMalloc((void**)dst, bytes));
-    if (!src.empty()) HIPOK(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+struct DevBuf {
+    T* p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p = o.p;
+            o.p = nullptr;
+        }
+        return *this;
+    }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { reset(); }
+    void reset() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+    int alloc(size_t n) {  // (never a null allocation: n = 0 holds one record)
+        reset();
+        HIPOK(hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)));
+        return RTG_OK;
+    }
+    int upload(const T* src, size_t n) {
+        if (int rc = alloc(n)) return rc;
+        if (n) HIPOK(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
+        return RTG_OK;
+    }
+    int upload(const std::vector<T>& src) { return upload(src.data(), src.size()); }
+    int download(T* dst, size_t n) const {
+        HIPOK(hipMemcpy(dst, p, n * sizeof(T), hipMemcpyDeviceToHost));
+        return RTG_OK;
+    }
+};
+
+// One device-code probe of the test suite on the null stream: `in` is uploaded, `out` allocated, and
+// launch(d) queues the kernel with d[k] the device copy of the k-th listed buffer (inputs, then
+// outputs); the outputs are copied back once it has run (a null dst: not wanted).
+struct ProbeIn { const void* src; size_t bytes; };
+struct ProbeOut { void* dst; size_t bytes; };
+template <class Launch>
+static int probe_run(std::initializer_list<ProbeIn> in, std::initializer_list<ProbeOut> out, Launch launch) {
+    std::vector<DevBuf<char>> buf(in.size() + out.size());
+    std::vector<void*> d;
+    for (const ProbeIn& i : in) {
+        if (int rc = buf[d.size()].upload((const char*)i.src, i.bytes)) return rc;
+        d.push_back(buf[d.size()].p);
+    }
+    for (const ProbeOut& o : out) {
+        if (int rc = buf[d.size()].alloc(o.bytes)) return rc;
+        d.push_back(buf[d.size()].p);
+    }
+    (void)hipGetLastError();  // (a stale error of other code on this thread is not this launch's)
+    launch(d.data());
+    HIPOK(hipGetLastError());
+    HIPOK(hipDeviceSynchronize());
+    size_t k = in.size();
+    for (const ProbeOut& o : out) {
+        if (o.dst) HIPOK(hipMemcpy(o.dst, d[k], o.bytes, hipMemcpyDeviceToHost));
+        ++k;
+    }
     return RTG_OK;
 }
 
@@ -321,6 +384,30 @@ struct ChunkSlot {
     bool used = false;          // fold has been recorded
 };
 
+// The scene's device records (upload_scene) and the tables of the opt-in shading modes, each built by
+// the first setting that needs it (a null pointer: not built, or nothing to build from). rtg_destroy
+// releases both on the handle's device, after its streams have drained.
+struct SceneBufs {
+    DevBuf<DevNode> nodes;
+    DevBuf<DevNodeQ> nodesq;
+    DevBuf<float4> leafbox;
+    DevBuf<float4> img;  // the small-scene image (SceneView::img)
+    DevBuf<DevTri48> tris48;
+    DevBuf<DevShade> shade;
+    DevBuf<DevMat> mats;
+    DevBuf<DevLight> lights;
+    DevBuf<DevTex> texinfo;
+    DevBuf<float> texels;
+};
+struct ModeTables {
+    DevBuf<uint4> env;            // rtg_set_env_sampling: one entry per cell of the environment map
+    DevBuf<uint4> light;          // rtg_set_light_sampling: one entry per light
+    DevBuf<PhysMat> phys;         // rtg_set_material_model: the unique parameter records
+    DevBuf<unsigned> phys_index;  // ... and one index into them per triangle
+    DevBuf<uint2> mis_index;      // rtg_set_path_mis: MisArgs::index
+    DevBuf<PhysMat> mis_ref;      // ... and reference-kind records for renders without the physical model
+};
+
 struct DenoiseState;  // rtg_denoise.hip
 struct TemporalState;  // rtg_temporal.hip
 
@@ -347,21 +434,12 @@ struct rtg_handle {
     SceneView sv{};
     DevCamera cam{};
     rtg_camera_proj proj{};  // projectOntoCamera state (light tracing, rtg_light.hip)
-    DevNode* d_nodes = nullptr;
-    DevNodeQ* d_nodesq = nullptr;
-    float4* d_leafbox = nullptr;
-    float4* d_img = nullptr;   // the small-scene image (SceneView::img)
+    SceneBufs scene;  // the records sv points to
     int usew = 0, wide = 1;
     int integrator = RTG_INTEGRATOR_PATH;
     rtg_camera_sampling cam_sampling{RTG_FILTER_NONE, 0.5f, 0.0f, 1.0f};  // rtg_set_camera_sampling
     bool rebuilt = false;     // wide tree cut from rebuild_over_leaves (else from the reference BVH2)
     uint32_t wide_depth = 0;  // wide levels on the longest root-to-leaf path
-    DevTri48* d_tris48 = nullptr;
-    DevShade* d_shade = nullptr;
-    DevMat* d_mats = nullptr;
-    DevLight* d_lights = nullptr;
-    DevTex* d_texinfo = nullptr;
-    float* d_texels = nullptr;
     float* d_film = nullptr;
     // chunk buffers (path state of the paths in flight), one set per slot; slot 0 also serves the
     // light tracer, instant radiosity and the ray queries (on `stream`)
@@ -402,7 +480,6 @@ struct rtg_handle {
     int env_mode = RTG_ENV_UNIFORM;
     bool env_light = false;       // the light list holds the environment light (upload_scene)
     bool env_built = false;       // the build has run (a black map leaves no table: the sampler stays uniform)
-    uint4* d_env_table = nullptr;
     std::vector<uint32_t> env_entries;  // the table's host copy (rtg_env_table)
     std::vector<double> env_weights;    // the cell weights it was built from (rtg_env_weights)
     double env_build_ms = 0.0;          // host time of the build: weights kernel, copy, Vose, upload
@@ -411,7 +488,6 @@ struct rtg_handle {
     rtg_light_sampling light_sampling{RTG_LIGHTS_UNIFORM, 0.125f};
     bool light_built = false;           // the build has run for light_built_share (a fallback leaves no table)
     float light_built_share = 0.0f;
-    uint4* d_light_table = nullptr;
     std::vector<uint32_t> light_entries;  // the table's host copy (rtg_light_table)
     std::vector<double> light_weights;    // the weights it was built from (rtg_light_weights)
     double light_build_ms = 0.0;
@@ -425,8 +501,6 @@ struct rtg_handle {
     bool phys_built = false;                   // the device table holds mat_params
     bool phys_any = false;                     // a triangle has a conductor, plastic or Oren-Nayar record
     bool trans_any = false;                    // a triangle has a rough dielectric record (k_shade_trans)
-    PhysMat* d_phys = nullptr;
-    unsigned* d_phys_index = nullptr;
     int n_phys = 0;
     std::vector<unsigned> phys_index;          // d_phys_index's host copy (rtg_set_path_mis's table takes it in)
     // rtg_set_path_mis (rtg_shade_mis.hip): the per-triangle table of k_shade_mis (MisArgs: the triangle ->
@@ -436,9 +510,8 @@ struct rtg_handle {
     int path_mis = RTG_PATH_MIS_OFF;
     std::vector<int32_t> light_tri;            // rtg_scene_desc.lights (upload_scene; host only)
     std::vector<int32_t> light_of;             // [triangle] -> light, the map's host copy (rtg_light_of_triangle)
-    uint2* d_mis_index = nullptr;
-    PhysMat* d_mis_ref = nullptr;
     int n_mis_ref = 0;
+    ModeTables mt;  // the device tables of the four settings above
 };
 #define RTG_CNT_PENDING 0xFFFFFFFFu
 
@@ -537,6 +610,10 @@ int flush_pending(rtg_handle* h);
 // the handle's stream waits for every queued chunk (called by every entry point that reads the film,
 // the stats or slot 0's buffers, or synchronises)
 int join_frames(rtg_handle* h);
+// ... on the handle's device, and has finished: what every setter does first (queued calls render with
+// the settings they were queued under) and every reader that copies with hipMemcpy, which does not
+// order against non-blocking streams
+int settle(rtg_handle* h);
 // the setting as the kernels take it, and its ChunkArgs::cam_mode
 static inline CamSampling cam_sampling_dev(const rtg_handle* h) {
     const rtg_camera_sampling& c = h->cam_sampling;
@@ -564,43 +641,53 @@ void denoise_drop_guides(rtg_handle* h);
 int camera_check(const char* who, const rtg_handle* h, const rtg_camera* cam, const rtg_camera_proj* proj);
 // rtg_temporal.hip: frees the handle's temporal state (rtg_destroy, rtg_temporal_reset)
 void temporal_release(rtg_handle* h);
-// rtg_env.hip: the table k_shade_env samples the environment light from under the handle's setting and
-// integrator, or one with a null pointer (uniform sampling: today's k_shade launches)
-EnvTable env_table_of(const rtg_handle* h);
 // rtg_env.hip: the environment map's w * h cell weights (the table's, and the environment light's weight
 // of rtg_set_light_sampling); waits for the handle's stream
 int env_cell_weights(rtg_handle* h, std::vector<double>& wts);
-// rtg_light_pick.hip: the table k_shade_pick picks the NEE light from under the handle's setting and
-// integrator, or one with a null pointer (the uniform pick: today's k_shade / k_shade_env launches)
-LightPick light_pick_of(const rtg_handle* h);
+// the environment table under the handle's setting, whatever its integrator (a null pointer: uniform sampling)
+static inline EnvTable env_table_set(const rtg_handle* h) {
+    if (h->env_mode != RTG_ENV_LUMINANCE || !h->mt.env.p) return EnvTable{nullptr, 0u, 0u, 0u};
+    const unsigned w = (unsigned)h->sv.env_w, hh = (unsigned)h->sv.env_h;
+    return EnvTable{h->mt.env.p, w * hh, w, hh};
+}
 // RTG_ERR_ARG (with "who: ..." as the message) for a setting outside include/rtg.h's ranges
 int light_sampling_check(const char* who, const rtg_light_sampling* p);
-// one k_shade_pick launch (ALT, TAB; ENV = env with a table) for bounce b
-int launch_shade_pick(bool alt, bool tab, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
-                      const PathBufs& p, int b, const EnvTable& env, const LightPick& pick);
-// rtg_shade_phys.hip: the table k_shade_phys shades from under the handle's setting and integrator, or
-// one with a null pointer (the reference model: today's launches)
-PhysArgs phys_args_of(const rtg_handle* h);
-// one k_shade_phys launch (ALT, TAB; the environment table and the light pick as runtime arguments)
-int launch_shade_phys(bool alt, bool tab, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
-                      const PathBufs& p, int b, const EnvTable& env, const LightPick& pick, const PhysArgs& phys);
 // rtg_shade_mis.hip: k_shade_mis's per-triangle table from the light list and the handle's parameter
 // index (a no-op before the first RTG_PATH_MIS_POWER setting); the caller has waited for the device
 int mis_sync_tables(rtg_handle* h);
-// rtg_shade_mis.hip: rtg_set_path_mis is on, the integrator is PATH and the map is built: k_shade_mis
-bool path_mis_active(const rtg_handle* h);
-// one k_shade_mis launch (TAB; the tables as runtime arguments, phys with a null table: the reference model)
-int launch_shade_mis(const rtg_handle* h, bool tab, unsigned grid, hipStream_t st, const ChunkArgs& a, const PathBufs& p,
-                     int b, const EnvTable& env, const LightPick& pick, const PhysArgs& phys);
-// rtg_shade_trans.hip: RTG_MATERIALS_PHYSICAL, a triangle with a rough dielectric record and PATH or DIRECT:
-// k_shade_trans (under rtg_set_path_mis's PATH: k_shade_trans_mis) in k_shade_phys's / k_shade_mis's place
-bool trans_active(const rtg_handle* h);
-// one launch of that family (phys: phys_args_of's table, which trans_active implies)
-int launch_shade_trans(const rtg_handle* h, bool alt, bool tab, unsigned grid, hipStream_t st, const ChunkArgs& a,
-                       const PathBufs& p, int b, const EnvTable& env, const LightPick& pick, const PhysArgs& phys);
 // RTG_ERR_ARG (with "who: ..." as the message) for records outside include/rtg.h's ranges
 int material_params_check(const char* who, const rtg_material_params* params, uint32_t n, uint32_t n_materials);
-// rtg_shade.hip: one k_shade launch of `grid` blocks (ALT = alt, TAB = tab) for bounce b
-// (env with a table: k_shade_env, the ALT kernel with the environment light's alias-table sample)
-int launch_shade(bool alt, bool tab, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
-                 const PathBufs& p, int b, const EnvTable* env = nullptr);
+
+// Which shading kernel a bounce runs, and with what: decided once per chunk by shade_mode_of
+// (rtg_render.hip) from the handle's settings, its integrator and the tables that are built.
+//   Plain     k_shade<alt, tab>                rtg_shade.hip       today's launches
+//   Env       k_shade_env<alt, tab>            rtg_shade.hip       RTG_ENV_LUMINANCE with a table
+//   Pick      k_shade_pick<alt, tab, env>      rtg_light_pick.hip  RTG_LIGHTS_POWER with a table
+//   Phys      k_shade_phys<alt, tab>           rtg_shade_phys.hip  RTG_MATERIALS_PHYSICAL with such a record
+//   Mis       k_shade_mis<tab>                 rtg_shade_mis.hip   RTG_PATH_MIS_POWER under PATH
+//   Trans     k_shade_trans<alt, tab>          rtg_shade_trans.hip ... with a rough dielectric record
+//   TransMis  k_shade_trans_mis<tab>           rtg_shade_trans.hip ... and RTG_PATH_MIS_POWER under PATH
+// From Phys on, the environment table and the light pick are run-time arguments (a null table: uniform).
+enum class ShadeFamily { Plain, Env, Pick, Phys, Mis, Trans, TransMis };
+struct ShadeMode {
+    ShadeFamily family;
+    bool alt;       // every per-pixel estimator (a.mode) instead of pathTrace alone
+    bool tab;       // the material, light and parameter records fit the kernel's LDS tables
+    EnvTable env;   // a null table: uniform sampling of the environment light
+    LightPick pick; // a null table: the uniform pick
+    PhysArgs phys;  // a null table: the reference model (Mis: reference-kind records for every index)
+    MisArgs mis;
+};
+ShadeMode shade_mode_of(const rtg_handle* h);
+// one shading launch of `grid` blocks for bounce b: each unit launches the kernels it defines
+// (launch_shade: Plain and Env; launch_shade_trans: Trans and TransMis)
+int launch_shade(const ShadeMode& m, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
+                 const PathBufs& p, int b);
+int launch_shade_pick(const ShadeMode& m, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
+                      const PathBufs& p, int b);
+int launch_shade_phys(const ShadeMode& m, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
+                      const PathBufs& p, int b);
+int launch_shade_mis(const ShadeMode& m, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
+                     const PathBufs& p, int b);
+int launch_shade_trans(const ShadeMode& m, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
+                       const PathBufs& p, int b);

@@ -477,14 +477,6 @@ __global__ __launch_bounds__(RTG_TB) void k_ir_splat(const unsigned* pixlist, un
 }
 
 // ------------------------------------------------------------------ host helpers
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { (void)hipFree(p); }
-    template <class T>
-    T* get() { return (T*)p; }
-};
-#define DALLOC(buf, bytes) HIPOK(hipMalloc(&(buf).p, std::max<size_t>((bytes), 16)))
-
 static DevProj make_proj(const rtg_handle* h) {
     DevProj c;
     std::memcpy(c.P, h->proj.proj, sizeof(c.P));
@@ -589,9 +581,16 @@ int rtg_render_light(rtg_handle* h, uint32_t first, uint32_t n_frames, uint64_t 
     if ((rc = ensure_ovf(h, h->slot[0]))) return rc;
     // records: at most one per path and vertex; grown on demand
     size_t cap = 4 * P + 1024;
-    DevBuf key, col, key2, idx, idx2, rn, tmp;
-    DALLOC(key, cap * 8); DALLOC(col, cap * 16); DALLOC(key2, cap * 8); DALLOC(idx, cap * 4); DALLOC(idx2, cap * 4);
-    DALLOC(rn, 16);
+    DevBuf<unsigned long long> key, key2;
+    DevBuf<float4> col;
+    DevBuf<unsigned> idx, idx2, rn;
+    DevBuf<char> tmp;
+    auto alloc_records = [&]() -> int {
+        int r;
+        if ((r = key.alloc(cap)) || (r = col.alloc(cap)) || (r = key2.alloc(cap)) || (r = idx.alloc(cap))) return r;
+        return idx2.alloc(cap);
+    };
+    if ((rc = alloc_records()) || (rc = rn.alloc(4))) return rc;
     size_t tmp_bytes = 0;
     const DevProj cam = make_proj(h);
     PathBufs& pb = h->slot[0].pb;
@@ -607,33 +606,27 @@ int rtg_render_light(rtg_handle* h, uint32_t first, uint32_t n_frames, uint64_t 
             for (;;) {  // grow the record buffers if a chunk overflows them (rare), then retry it
                 // every attempt of every chunk starts without records, as instant radiosity's loop does
                 HIPOK(hipMemsetAsync(rn.p, 0, 16, st));
-                rc = trace_light_paths(h, st, a, pb, key.get<unsigned long long>(), col.get<float4>(), rn.get<unsigned>(), cap);
+                rc = trace_light_paths(h, st, a, pb, key.p, col.p, rn.p, cap);
                 if (rc == RTG_OK) break;
                 if (g_err != "light tracing: record buffer overflow") return rc;
                 cap *= 4;
-                (void)hipFree(key.p); (void)hipFree(col.p); (void)hipFree(key2.p); (void)hipFree(idx.p); (void)hipFree(idx2.p);
-                key.p = col.p = key2.p = idx.p = idx2.p = nullptr;
-                DALLOC(key, cap * 8); DALLOC(col, cap * 16); DALLOC(key2, cap * 8); DALLOC(idx, cap * 4); DALLOC(idx2, cap * 4);
+                if ((rc = alloc_records())) return rc;
             }
             unsigned n = 0;
             HIPOK(hipMemcpyAsync(&n, rn.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
             HIPOK(hipStreamSynchronize(st));
             if (n == 0) continue;
-            hipLaunchKernelGGL(k_iota, dim3(grid(n)), dim3(RTG_TB), 0, st, idx.get<unsigned>(), n);
+            hipLaunchKernelGGL(k_iota, dim3(grid(n)), dim3(RTG_TB), 0, st, idx.p, n);
             LAUNCH_OK("k_iota");
             size_t need = 0;
-            HIPOK(rocprim::radix_sort_pairs(nullptr, need, key.get<unsigned long long>(), key2.get<unsigned long long>(),
-                                            idx.get<unsigned>(), idx2.get<unsigned>(), n, 0, 64, st));
+            HIPOK(rocprim::radix_sort_pairs(nullptr, need, key.p, key2.p, idx.p, idx2.p, n, 0, 64, st));
             if (need > tmp_bytes) {
-                (void)hipFree(tmp.p);
-                tmp.p = nullptr;
-                DALLOC(tmp, need);
+                if ((rc = tmp.alloc(need))) return rc;
                 tmp_bytes = need;
             }
-            HIPOK(rocprim::radix_sort_pairs(tmp.p, need, key.get<unsigned long long>(), key2.get<unsigned long long>(),
-                                            idx.get<unsigned>(), idx2.get<unsigned>(), n, 0, 64, st));
-            hipLaunchKernelGGL(k_light_splat, dim3(grid(n)), dim3(RTG_TB), 0, st, key2.get<unsigned long long>(),
-                               idx2.get<unsigned>(), (const float4*)col.p, n, (unsigned)npaths, h->d_film);
+            HIPOK(rocprim::radix_sort_pairs((void*)tmp.p, need, key.p, key2.p, idx.p, idx2.p, n, 0, 64, st));
+            hipLaunchKernelGGL(k_light_splat, dim3(grid(n)), dim3(RTG_TB), 0, st, key2.p, idx2.p, (const float4*)col.p, n,
+                               (unsigned)npaths, h->d_film);
             LAUNCH_OK("k_light_splat");
         }
         h->spp += 1;  // render(): film->incrementSPP()
@@ -657,9 +650,11 @@ int rtg_render_instant_radiosity(rtg_handle* h, uint32_t first, uint32_t n_frame
     PathBufs& pb = h->slot[0].pb;
     const DevProj cam = make_proj(h);
     size_t cap = 64 * (size_t)n_vpl + 1024;
-    DevBuf vkey, vrec, rn, px, pn, pf, acc, vpl_d;
-    DALLOC(vkey, cap * 8); DALLOC(vrec, cap * 48); DALLOC(rn, 16);
-    DALLOC(px, (size_t)npix * 16); DALLOC(pn, (size_t)npix * 16); DALLOC(pf, (size_t)npix * 16); DALLOC(acc, (size_t)npix * 16);
+    DevBuf<unsigned long long> vkey;
+    DevBuf<float4> vrec, px, pn, pf, acc, vpl_d;  // (vrec, vpl_d: three float4 per record)
+    DevBuf<unsigned> rn;
+    if ((rc = vkey.alloc(cap)) || (rc = vrec.alloc(cap * 3)) || (rc = rn.alloc(4))) return rc;
+    if ((rc = px.alloc(npix)) || (rc = pn.alloc(npix)) || (rc = pf.alloc(npix)) || (rc = acc.alloc(npix))) return rc;
     for (uint32_t f = first; f < first + n_frames; ++f) {
         // ---- traceVPLs (Renderer.h:183-206)
         LightArgs a{};
@@ -672,13 +667,11 @@ int rtg_render_instant_radiosity(rtg_handle* h, uint32_t first, uint32_t n_frame
         a.cam = cam;
         for (;;) {
             HIPOK(hipMemsetAsync(rn.p, 0, 16, st));
-            rc = trace_light_paths(h, st, a, pb, vkey.get<unsigned long long>(), vrec.get<float4>(), rn.get<unsigned>(), cap);
+            rc = trace_light_paths(h, st, a, pb, vkey.p, vrec.p, rn.p, cap);
             if (rc == RTG_OK) break;
             if (g_err != "light tracing: record buffer overflow") return rc;
             cap *= 4;
-            (void)hipFree(vkey.p); (void)hipFree(vrec.p);
-            vkey.p = vrec.p = nullptr;
-            DALLOC(vkey, cap * 8); DALLOC(vrec, cap * 48);
+            if ((rc = vkey.alloc(cap)) || (rc = vrec.alloc(cap * 3))) return rc;
         }
         unsigned nv = 0;
         HIPOK(hipMemcpy(&nv, rn.p, sizeof(unsigned), hipMemcpyDeviceToHost));
@@ -694,10 +687,7 @@ int rtg_render_instant_radiosity(rtg_handle* h, uint32_t first, uint32_t n_frame
         std::sort(order.begin(), order.end(), [&](unsigned x, unsigned y) { return hk[x] < hk[y]; });
         for (unsigned i = 0; i < nv; ++i)
             for (int c = 0; c < 3; ++c) vl[3 * i + c] = hr[3 * (size_t)order[i] + c];
-        (void)hipFree(vpl_d.p);
-        vpl_d.p = nullptr;
-        DALLOC(vpl_d, vl.size() * 16);
-        HIPOK(hipMemcpy(vpl_d.p, vl.data(), vl.size() * 16, hipMemcpyHostToDevice));
+        if ((rc = vpl_d.upload(vl))) return rc;
         // ---- camera rays and first hits (renderBlockinstantRadiosity, Renderer.h:83-100)
         ChunkArgs ca{};
         ca.pixlist = h->d_pix;
@@ -725,39 +715,40 @@ int rtg_render_instant_radiosity(rtg_handle* h, uint32_t first, uint32_t n_frame
         if ((rc = launch_trace(h, io, st))) return rc;
         if ((rc = tally_rays(h, st, npix, 0))) return rc;
         h->stats.paths += npix;
-        hipLaunchKernelGGL(k_ir_first_hit, dim3(grid(npix)), dim3(RTG_TB), 0, st, h->sv, ca, pb, px.get<float4>(),
-                           pn.get<float4>(), pf.get<float4>(), acc.get<float4>());
+        hipLaunchKernelGGL(k_ir_first_hit, dim3(grid(npix)), dim3(RTG_TB), 0, st, h->sv, ca, pb, px.p, pn.p, pf.p, acc.p);
         LAUNCH_OK("k_ir_first_hit");
         // ---- every pixel x every VPL, in VPL batches (computeVPLsContribution, Renderer.h:125-156)
         if (nv) {
             const unsigned nb = (unsigned)std::max<size_t>(1, std::min<size_t>(nv, h->max_paths / std::max(1u, npix)));
             const size_t R = (size_t)npix * nb;
-            DevBuf so, sd, q, vis, qn;
-            DALLOC(so, R * 16); DALLOC(sd, R * 16); DALLOC(q, R * 4); DALLOC(vis, R * 4); DALLOC(qn, 16);
+            DevBuf<float4> so, sd;
+            DevBuf<unsigned> q, qn;
+            DevBuf<int> vis;
+            if ((rc = so.alloc(R)) || (rc = sd.alloc(R)) || (rc = q.alloc(R)) || (rc = vis.alloc(R)) || (rc = qn.alloc(4)))
+                return rc;
             for (unsigned j0 = 0; j0 < nv; j0 += nb) {
                 const unsigned b = std::min(nb, nv - j0);
                 const size_t Rb = (size_t)npix * b;
                 HIPOK(hipMemsetAsync(qn.p, 0, 16, st));
                 HIPOK(hipMemsetAsync(vis.p, 0, Rb * 4, st));
                 hipLaunchKernelGGL(k_ir_rays, dim3(grid(Rb)), dim3(RTG_TB), 0, st, npix, (const float4*)px.p,
-                                   (const float4*)pn.p, (const float4*)vpl_d.p, j0, b, so.get<float4>(), sd.get<float4>(),
-                                   q.get<unsigned>(), qn.get<unsigned>());
+                                   (const float4*)pn.p, (const float4*)vpl_d.p, j0, b, so.p, sd.p, q.p, qn.p);
                 LAUNCH_OK("k_ir_rays");
                 TraceIO sio{};
                 sio.stats = h->d_stats;
                 sio.cull = h->cull;
                 sio.wide = h->wide;
                 sio.ovf = h->slot[0].d_ovf;
-                sio.squeue = q.get<unsigned>();
-                sio.sray_o = so.get<float4>();
-                sio.sray_d = sd.get<float4>();
-                sio.scount = qn.get<unsigned>();
-                sio.visible = vis.get<int>();
-                sio.fetch = qn.get<unsigned>() + 1;
+                sio.squeue = q.p;
+                sio.sray_o = so.p;
+                sio.sray_d = sd.p;
+                sio.scount = qn.p;
+                sio.visible = vis.p;
+                sio.fetch = qn.p + 1;
                 if ((rc = launch_trace(h, sio, st))) return rc;
                 hipLaunchKernelGGL(k_ir_accumulate, dim3(grid(npix)), dim3(RTG_TB), 0, st, npix, (const float4*)px.p,
                                    (const float4*)pn.p, (const float4*)pf.p, (const float4*)vpl_d.p, j0, b,
-                                   (const int*)vis.p, acc.get<float4>());
+                                   (const int*)vis.p, acc.p);
                 LAUNCH_OK("k_ir_accumulate");
                 unsigned ns = 0;
                 HIPOK(hipMemcpyAsync(&ns, qn.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
@@ -780,19 +771,11 @@ int rtg_probe_connect(rtg_handle* h, const float* points, const float* normals, 
     if (n > 0x7fffffffu / 12u) { g_err = "rtg_probe_connect: too many points"; return RTG_ERR_ARG; }
     if (n == 0) return RTG_OK;
     HIPOK(hipSetDevice(h->device));
-    DevBuf d_pts, d_nrm, d_col, d_out;
     const size_t in_bytes = (size_t)n * 3 * sizeof(float), out_bytes = (size_t)n * 12 * sizeof(float);
-    DALLOC(d_pts, in_bytes); DALLOC(d_nrm, in_bytes); DALLOC(d_col, in_bytes); DALLOC(d_out, out_bytes);
-    HIPOK(hipMemcpy(d_pts.p, points, in_bytes, hipMemcpyHostToDevice));
-    HIPOK(hipMemcpy(d_nrm.p, normals, in_bytes, hipMemcpyHostToDevice));
-    HIPOK(hipMemcpy(d_col.p, colours, in_bytes, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_probe_connect, dim3((n + 255) / 256), dim3(256), 0, nullptr, make_proj(h),
-                       (const float*)d_pts.p, (const float*)d_nrm.p, (const float*)d_col.p, (unsigned)n,
-                       d_out.get<float>());
-    HIPOK(hipGetLastError());
-    HIPOK(hipDeviceSynchronize());
-    HIPOK(hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost));
-    return RTG_OK;
+    return probe_run({{points, in_bytes}, {normals, in_bytes}, {colours, in_bytes}}, {{out, out_bytes}}, [&](void* const* d) {
+        hipLaunchKernelGGL(k_probe_connect, dim3((n + 255) / 256), dim3(256), 0, nullptr, make_proj(h), (const float*)d[0],
+                           (const float*)d[1], (const float*)d[2], (unsigned)n, (float*)d[3]);
+    });
 }
 
 }  // extern "C"

@@ -33,26 +33,20 @@ __global__ void k_probe_light_pick(LightPick lpk, unsigned nl, const unsigned* r
     pmf[i] = pm;
 }
 
-int launch_shade_pick(bool alt, bool tab, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
-                      const PathBufs& p, int b, const EnvTable& env, const LightPick& pick) {
-    const int sel = (alt ? 4 : 0) | (tab ? 2 : 0) | (env.table ? 1 : 0);
+int launch_shade_pick(const ShadeMode& m, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
+                      const PathBufs& p, int b) {
+    const int sel = (m.alt ? 4 : 0) | (m.tab ? 2 : 0) | (m.env.table ? 1 : 0);
     void (*const kern[8])(SceneView, ChunkArgs, PathBufs, int, EnvTable, LightPick) = {
         k_shade_pick<false, false, false>, k_shade_pick<false, false, true>, k_shade_pick<false, true, false>,
         k_shade_pick<false, true, true>,   k_shade_pick<true, false, false>, k_shade_pick<true, false, true>,
         k_shade_pick<true, true, false>,   k_shade_pick<true, true, true>};
-    hipLaunchKernelGGL(kern[sel], dim3(grid), dim3(RTG_TB), 0, st, s, a, p, b, env, pick);
+    hipLaunchKernelGGL(kern[sel], dim3(grid), dim3(RTG_TB), 0, st, s, a, p, b, m.env, m.pick);
     LAUNCH_OK("k_shade_pick");
     return RTG_OK;
 }
 
 static bool pick_active(const rtg_handle* h) {
-    return h->light_sampling.mode == RTG_LIGHTS_POWER && h->d_light_table != nullptr;
-}
-
-LightPick light_pick_of(const rtg_handle* h) {
-    const bool picks_light = h->integrator == RTG_INTEGRATOR_PATH || h->integrator == RTG_INTEGRATOR_DIRECT ||
-                             h->integrator == RTG_INTEGRATOR_DIRECT_MIS;
-    return LightPick{(pick_active(h) && picks_light) ? h->d_light_table : nullptr};
+    return h->light_sampling.mode == RTG_LIGHTS_POWER && h->mt.light.p != nullptr;
 }
 
 static bool finite_d(double x) { return x == x && x <= 1.7976931348623157e308 && x >= -1.7976931348623157e308; }
@@ -94,49 +88,37 @@ static int build_light_table(rtg_handle* h, float share) {
     std::vector<DevLight> rec(n);
     std::vector<double> wts(n, 0.0), pmf;
     std::vector<uint32_t> entries((size_t)n * 4);
-    uint4* d_tab = nullptr;
-    bool have = false;
-    auto run = [&]() -> int {
-        HIPOK(hipMemcpy(rec.data(), h->d_lights, (size_t)n * sizeof(DevLight), hipMemcpyDeviceToHost));
-        bool ok = n > 1;
-        for (uint32_t i = 0; i < n && ok; ++i) {
-            const DevLight& L = rec[i];
-            int type;
-            std::memcpy(&type, &L.v1t.w, 4);
-            if (type == 0) {
-                const float l = ((0.2126f * L.em.x) + (0.7152f * L.em.y)) + (0.0722f * L.em.z);  // Colour::Lum
-                const float c = (l > 0.0f && l <= RTG_FLT_MAX) ? l : 0.0f;
-                wts[i] = (double)c * (double)L.v0a.w;
-            } else {
-                const float* rb = h->sv.root_box;
-                const double dx = (double)rb[3] - (double)rb[0], dy = (double)rb[4] - (double)rb[1],
-                             dz = (double)rb[5] - (double)rb[2];
-                const double R = 0.5 * std::sqrt((dx * dx + dy * dy) + dz * dz);
-                if (!(R > 0.0) || !finite_d(R) || h->sv.env_tex < 0) { ok = false; break; }
-                std::vector<double> own;  // (the §8c weights: the environment table's when it was built)
-                if (!h->env_built)
-                    if (int rc = env_cell_weights(h, own)) return rc;
-                const std::vector<double>& cw = h->env_built ? h->env_weights : own;
-                double S = 0.0;
-                for (double x : cw) S += x;
-                const double pi = 3.14159265358979323846;
-                wts[i] = (2.0 * pi * pi) * R * R * (S / (double)cw.size());
-            }
+    DevBuf<uint4> d_tab;
+    if (int rc = h->scene.lights.download(rec.data(), n)) return rc;
+    bool ok = n > 1;
+    for (uint32_t i = 0; i < n && ok; ++i) {
+        const DevLight& L = rec[i];
+        int type;
+        std::memcpy(&type, &L.v1t.w, 4);
+        if (type == 0) {
+            const float l = ((0.2126f * L.em.x) + (0.7152f * L.em.y)) + (0.0722f * L.em.z);  // Colour::Lum
+            const float c = (l > 0.0f && l <= RTG_FLT_MAX) ? l : 0.0f;
+            wts[i] = (double)c * (double)L.v0a.w;
+        } else {
+            const float* rb = h->sv.root_box;
+            const double dx = (double)rb[3] - (double)rb[0], dy = (double)rb[4] - (double)rb[1],
+                         dz = (double)rb[5] - (double)rb[2];
+            const double R = 0.5 * std::sqrt((dx * dx + dy * dy) + dz * dz);
+            if (!(R > 0.0) || !finite_d(R) || h->sv.env_tex < 0) { ok = false; break; }
+            std::vector<double> own;  // (the §8c weights: the environment table's when it was built)
+            if (!h->env_built)
+                if (int rc = env_cell_weights(h, own)) return rc;
+            const std::vector<double>& cw = h->env_built ? h->env_weights : own;
+            double S = 0.0;
+            for (double x : cw) S += x;
+            const double pi = 3.14159265358979323846;
+            wts[i] = (2.0 * pi * pi) * R * R * (S / (double)cw.size());
         }
-        rtg_env::Alias al;
-        have = ok && build_pick(wts.data(), n, (double)share, pmf, al, entries.data());
-        if (!have) return RTG_OK;
-        HIPOK(hipMalloc((void**)&d_tab, (size_t)n * 16));
-        HIPOK(hipMemcpy(d_tab, entries.data(), (size_t)n * 16, hipMemcpyHostToDevice));
-        return RTG_OK;
-    };
-    const int rc = run();
-    if (rc != RTG_OK) {
-        (void)hipFree(d_tab);
-        return rc;
     }
-    (void)hipFree(h->d_light_table);
-    h->d_light_table = have ? d_tab : nullptr;
+    rtg_env::Alias al;
+    if (ok && build_pick(wts.data(), n, (double)share, pmf, al, entries.data()))
+        if (int rc = d_tab.upload((const uint4*)entries.data(), n)) return rc;
+    h->mt.light = std::move(d_tab);
     h->light_built = true;
     h->light_built_share = share;
     h->light_entries.swap(entries);
@@ -170,9 +152,7 @@ int rtg_light_sampling_defaults(rtg_light_sampling* p) {
 int rtg_set_light_sampling(rtg_handle* h, const rtg_light_sampling* p) {
     if (!h) { g_err = "rtg_set_light_sampling: null handle"; return RTG_ERR_ARG; }
     if (int rc = light_sampling_check("rtg_set_light_sampling", p)) return rc;
-    HIPOK(hipSetDevice(h->device));
-    if (int rc = join_frames(h)) return rc;  // queued calls render with the settings they were queued under
-    HIPOK(hipStreamSynchronize(h->stream));
+    if (int rc = settle(h)) return rc;
     if (p->mode == RTG_LIGHTS_POWER && (!h->light_built || h->light_built_share != p->uniform_share))
         if (int rc = build_light_table(h, p->uniform_share)) return rc;
     h->light_sampling = *p;
@@ -206,8 +186,7 @@ int rtg_light_records(rtg_handle* h, float* out) {
     if (!h || !out) { g_err = "rtg_light_records: null argument"; return RTG_ERR_ARG; }
     static_assert(sizeof(DevLight) == 20 * sizeof(float), "rtg_light_records: 20 floats per light");
     HIPOK(hipSetDevice(h->device));
-    HIPOK(hipMemcpy(out, h->d_lights, (size_t)h->sv.n_lights * sizeof(DevLight), hipMemcpyDeviceToHost));
-    return RTG_OK;
+    return h->scene.lights.download((DevLight*)out, (size_t)h->sv.n_lights);
 }
 
 int rtg_probe_light_pick(rtg_handle* h, const uint32_t* r0, const float* d1, uint32_t n, int32_t* li, float* pmf) {
@@ -216,31 +195,12 @@ int rtg_probe_light_pick(rtg_handle* h, const uint32_t* r0, const float* d1, uin
     if (n > 0x7fffffffu / 4u) { g_err = "rtg_probe_light_pick: too many cases"; return RTG_ERR_ARG; }
     if (n == 0) return RTG_OK;
     HIPOK(hipSetDevice(h->device));
-    unsigned* d_r = nullptr;
-    float *d_d = nullptr, *d_pmf = nullptr;
-    int* d_li = nullptr;
-    auto run = [&]() -> int {
-        HIPOK(hipMalloc((void**)&d_r, (size_t)n * sizeof(unsigned)));
-        HIPOK(hipMalloc((void**)&d_d, (size_t)n * sizeof(float)));
-        HIPOK(hipMalloc((void**)&d_li, (size_t)n * sizeof(int)));
-        HIPOK(hipMalloc((void**)&d_pmf, (size_t)n * sizeof(float)));
-        HIPOK(hipMemcpy(d_r, r0, (size_t)n * sizeof(unsigned), hipMemcpyHostToDevice));
-        HIPOK(hipMemcpy(d_d, d1, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-        (void)hipGetLastError();  // (a stale error of other code on this thread is not this launch's)
-        hipLaunchKernelGGL(k_probe_light_pick, dim3((n + 255) / 256), dim3(256), 0, nullptr, LightPick{h->d_light_table},
-                           (unsigned)h->sv.n_lights, (const unsigned*)d_r, (const float*)d_d, (unsigned)n, d_li, d_pmf);
-        HIPOK(hipGetLastError());
-        HIPOK(hipDeviceSynchronize());
-        HIPOK(hipMemcpy(li, d_li, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-        HIPOK(hipMemcpy(pmf, d_pmf, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-        return RTG_OK;
-    };
-    const int rc = run();
-    (void)hipFree(d_r);
-    (void)hipFree(d_d);
-    (void)hipFree(d_li);
-    (void)hipFree(d_pmf);
-    return rc;
+    const size_t bytes = (size_t)n * 4;  // (every buffer holds n 4-byte values)
+    return probe_run({{r0, bytes}, {d1, bytes}}, {{li, bytes}, {pmf, bytes}}, [&](void* const* d) {
+        hipLaunchKernelGGL(k_probe_light_pick, dim3((n + 255) / 256), dim3(256), 0, nullptr, LightPick{h->mt.light.p},
+                           (unsigned)h->sv.n_lights, (const unsigned*)d[0], (const float*)d[1], (unsigned)n, (int*)d[2],
+                           (float*)d[3]);
+    });
 }
 
 int rtg_light_pick_build(const double* weights, uint32_t n, double uniform_share, double* pmf, double* prob,

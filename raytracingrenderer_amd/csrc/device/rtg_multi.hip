@@ -132,11 +132,11 @@ struct rtg_group {
     float* d_sum = nullptr;                    // assembled film on devices[0]
     // own-tile exchange: rank r's pixel list and pack buffer on its device (npix[r] pixels); on
     // devices[0] the receive buffer (rank r's pixels at r * maxpix) and the matching pixel lists
-    std::vector<uint32_t*> d_pix;
+    std::vector<DevBuf<uint32_t>> d_pix;
     std::vector<float*> d_pack;
     std::vector<uint32_t> npix;
     uint32_t maxpix = 0;
-    uint32_t* d_pix_all = nullptr;
+    DevBuf<uint32_t> d_pix_all;
     float* d_recv = nullptr;
     uint32_t W = 0, H = 0;
     uint32_t reduced_spp = 0;
@@ -173,17 +173,17 @@ static int exchange_setup(rtg_group* g) {
     for (size_t r = 0; r < n; ++r) std::copy(pl[r].begin(), pl[r].end(), all.begin() + r * mp);
     HIPOK(hipSetDevice(g->devices[0]));
     HIPOK(hipMalloc((void**)&g->d_recv, n * mp * 3 * sizeof(float)));
-    if (dev_upload(&g->d_pix_all, all)) return RTG_ERR_HIP;
+    if (g->d_pix_all.upload(all)) return RTG_ERR_HIP;
     HIPOK(hipEventCreate(&g->xe0));
     HIPOK(hipEventCreate(&g->xe1));
     HIPOK(hipEventCreateWithFlags(&g->xcopied, hipEventDisableTiming));
-    g->d_pix.assign(n, nullptr);
+    g->d_pix.resize(n);
     g->d_pack.assign(n, nullptr);
     g->xs.assign(n, nullptr);
     g->xpacked.assign(n, nullptr);
     for (size_t r = 0; r < n; ++r) {
         HIPOK(hipSetDevice(g->devices[r]));
-        if (dev_upload(&g->d_pix[r], pl[r])) return RTG_ERR_HIP;
+        if (g->d_pix[r].upload(pl[r])) return RTG_ERR_HIP;
         if (r == 0 && !g->rccl_self) g->d_pack[r] = g->d_recv;
         else HIPOK(hipMalloc((void**)&g->d_pack[r], mp * 3 * sizeof(float)));
         HIPOK(hipStreamCreateWithFlags(&g->xs[r], hipStreamNonBlocking));
@@ -217,6 +217,25 @@ static int for_ranks(rtg_group* g, F fn) {
             g_err = "rank " + std::to_string(r) + ": " + err[r] + " (group films now partial: rtg_group_clear)";
             return rc[r];
         }
+    return RTG_OK;
+}
+
+// A setting that can fail on the device (its table is built per rank): set(h, v) on every rank, and when
+// a rank fails the earlier ranks go back to what get(h, &prev) read from it (the ranks hold one
+// setting), so the group stays as it was. Argument errors are checked once by the caller, before.
+template <class T, class Get, class Set>
+static int set_all_or_restore(rtg_group* g, const T& v, Get get, Set set) {
+    for (rtg_handle* h : g->h) {
+        T prev = v;
+        (void)get(h, &prev);
+        if (const int rc = set(h, v)) {
+            for (rtg_handle* u : g->h) {
+                if (u == h) break;
+                (void)set(u, prev);
+            }
+            return rc;
+        }
+    }
     return RTG_OK;
 }
 
@@ -321,7 +340,7 @@ void rtg_group_destroy(rtg_group* g) {
     for (ncclComm_t c : g->comms) (void)g_rccl.comm_destroy(c);
     for (size_t r = 0; r < g->d_pix.size(); ++r) {
         (void)hipSetDevice(g->devices[r]);
-        (void)hipFree(g->d_pix[r]);
+        g->d_pix[r].reset();
         if (r > 0 || g->rccl_self) (void)hipFree(g->d_pack[r]);  // rank 0 packs straight into d_recv
         if (r < g->xs.size() && g->xs[r]) (void)hipStreamDestroy(g->xs[r]);
         if (r < g->xpacked.size() && g->xpacked[r]) (void)hipEventDestroy(g->xpacked[r]);
@@ -330,7 +349,7 @@ void rtg_group_destroy(rtg_group* g) {
         (void)hipSetDevice(g->devices[0]);
         (void)hipFree(g->d_sum);
         (void)hipFree(g->d_recv);
-        (void)hipFree(g->d_pix_all);
+        g->d_pix_all.reset();
         if (g->xe0) (void)hipEventDestroy(g->xe0);
         if (g->xe1) (void)hipEventDestroy(g->xe1);
         if (g->xcopied) (void)hipEventDestroy(g->xcopied);
@@ -473,19 +492,7 @@ int rtg_group_set_env_sampling(rtg_group* g, int mode) {
     // checked once for all ranks (they hold the same scene), so an argument error leaves every rank's
     // setting as it was; every rank builds its own table, the same bits from the same texels
     if (int rc = rtg_env_sampling_check(mode, 0, 0)) return rc;
-    for (rtg_handle* h : g->h) {
-        int prev = RTG_ENV_UNIFORM;
-        (void)rtg_get_env_sampling(h, &prev);
-        const int rc = rtg_set_env_sampling(h, mode);
-        if (rc) {
-            for (rtg_handle* u : g->h) {
-                if (u == h) break;
-                (void)rtg_set_env_sampling(u, prev);
-            }
-            return rc;
-        }
-    }
-    return RTG_OK;
+    return set_all_or_restore(g, mode, rtg_get_env_sampling, rtg_set_env_sampling);
 }
 
 int rtg_group_set_light_sampling(rtg_group* g, const rtg_light_sampling* p) {
@@ -493,19 +500,8 @@ int rtg_group_set_light_sampling(rtg_group* g, const rtg_light_sampling* p) {
     // checked once for all ranks, so an argument error leaves every rank's setting as it was; every rank
     // builds its own table, the same bits from the same records
     if (int rc = light_sampling_check("rtg_group_set_light_sampling", p)) return rc;
-    for (rtg_handle* h : g->h) {
-        rtg_light_sampling prev{RTG_LIGHTS_UNIFORM, 0.125f};
-        (void)rtg_get_light_sampling(h, &prev);
-        const int rc = rtg_set_light_sampling(h, p);
-        if (rc) {
-            for (rtg_handle* u : g->h) {
-                if (u == h) break;
-                (void)rtg_set_light_sampling(u, &prev);
-            }
-            return rc;
-        }
-    }
-    return RTG_OK;
+    return set_all_or_restore(g, *p, rtg_get_light_sampling,
+                              [](rtg_handle* h, const rtg_light_sampling& v) { return rtg_set_light_sampling(h, &v); });
 }
 
 int rtg_group_set_material_params(rtg_group* g, const rtg_material_params* params, uint32_t n) {
@@ -520,19 +516,7 @@ int rtg_group_set_material_params(rtg_group* g, const rtg_material_params* param
 
 int rtg_group_set_material_model(rtg_group* g, int mode) {
     if (!g) { g_err = "rtg_group_set_material_model: null group"; return RTG_ERR_ARG; }
-    for (rtg_handle* h : g->h) {
-        int prev = RTG_MATERIALS_REFERENCE;
-        (void)rtg_get_material_model(h, &prev);
-        const int rc = rtg_set_material_model(h, mode);
-        if (rc) {
-            for (rtg_handle* u : g->h) {
-                if (u == h) break;
-                (void)rtg_set_material_model(u, prev);
-            }
-            return rc;
-        }
-    }
-    return RTG_OK;
+    return set_all_or_restore(g, mode, rtg_get_material_model, rtg_set_material_model);
 }
 
 int rtg_group_set_camera(rtg_group* g, const rtg_camera* cam, const rtg_camera_proj* proj) {
@@ -550,19 +534,7 @@ int rtg_group_set_path_mis(rtg_group* g, int mode) {
     if (!g) { g_err = "rtg_group_set_path_mis: null group"; return RTG_ERR_ARG; }
     // checked once for all ranks, so an argument error leaves every rank's setting as it was
     if (int rc = rtg_path_mis_check(mode)) return rc;
-    for (rtg_handle* h : g->h) {
-        int prev = RTG_PATH_MIS_OFF;
-        (void)rtg_get_path_mis(h, &prev);
-        const int rc = rtg_set_path_mis(h, mode);
-        if (rc) {
-            for (rtg_handle* u : g->h) {
-                if (u == h) break;
-                (void)rtg_set_path_mis(u, prev);
-            }
-            return rc;
-        }
-    }
-    return RTG_OK;
+    return set_all_or_restore(g, mode, rtg_get_path_mis, rtg_set_path_mis);
 }
 
 int rtg_group_render(rtg_group* g, uint32_t first_sample, uint32_t n_samples, uint64_t seed) {
@@ -623,7 +595,7 @@ int rtg_group_reduce_async(rtg_group* g) {
     }
     // every rank packs its own tiles' pixels on its device (rank 0 straight into the receive buffer)
     for (size_t r = 0; r < n; ++r)
-        if (int rc = rtg_film_gather(g->h[r], g->d_pix[r], g->npix[r], g->d_pack[r], g->xs[r])) return rc;
+        if (int rc = rtg_film_gather(g->h[r], g->d_pix[r].p, g->npix[r], g->d_pack[r], g->xs[r])) return rc;
     if (!g->comms.empty()) {
         // one ncclSend per rank > 0 to device 0, which posts the matching ncclRecv into slot r of its
         // receive buffer. Every failure inside the group still closes it (ncclGroupEnd), so the
@@ -661,7 +633,7 @@ int rtg_group_reduce_async(rtg_group* g) {
         }
     }
     // tile supports cover the film, so the scatter writes every pixel of d_sum
-    if (int rc = rtg_film_scatter(g->devices[0], g->d_recv, g->d_pix_all, (uint32_t)(n * mp), g->d_sum, film_pixels,
+    if (int rc = rtg_film_scatter(g->devices[0], g->d_recv, g->d_pix_all.p, (uint32_t)(n * mp), g->d_sum, film_pixels,
                                   g->xs[0]))
         return rc;
     HIPOK(hipEventRecord(g->xe1, g->xs[0]));

@@ -339,6 +339,50 @@ int join_frames(rtg_handle* h) {
     return RTG_OK;
 }
 
+int settle(rtg_handle* h) {
+    HIPOK(hipSetDevice(h->device));
+    if (int rc = join_frames(h)) return rc;
+    HIPOK(hipStreamSynchronize(h->stream));
+    return RTG_OK;
+}
+
+// The one place that decides a frame's shading kernel (rtg_internal.h has the families)
+ShadeMode shade_mode_of(const rtg_handle* h) {
+    const int in = h->integrator;
+    const bool path = in == RTG_INTEGRATOR_PATH, direct = in == RTG_INTEGRATOR_DIRECT;
+    const bool samples_light = path || direct || in == RTG_INTEGRATOR_DIRECT_MIS;
+    const bool physical = h->material_model == RTG_MATERIALS_PHYSICAL && h->phys_built && (path || direct);
+    const bool mis = h->path_mis == RTG_PATH_MIS_POWER && path && h->mt.mis_index.p != nullptr;
+    ShadeMode m{};
+    m.alt = !path;
+    m.env = samples_light ? env_table_set(h) : EnvTable{nullptr, 0u, 0u, 0u};
+    m.pick = LightPick{samples_light && h->light_sampling.mode == RTG_LIGHTS_POWER ? h->mt.light.p : nullptr};
+    m.phys = physical && h->phys_any ? PhysArgs{h->mt.phys.p, h->mt.phys_index.p, h->n_phys} : PhysArgs{nullptr, nullptr, 0};
+    m.mis = MisArgs{mis ? h->mt.mis_index.p : nullptr};
+    if (physical && h->trans_any) m.family = mis ? ShadeFamily::TransMis : ShadeFamily::Trans;
+    else if (mis) m.family = ShadeFamily::Mis;
+    else if (m.phys.table) m.family = ShadeFamily::Phys;
+    else if (m.pick.table) m.family = ShadeFamily::Pick;
+    else m.family = m.env.table ? ShadeFamily::Env : ShadeFamily::Plain;
+    // k_shade_mis under the reference model, or in a scene without a physical record: reference-kind
+    // records for every index
+    if (m.family == ShadeFamily::Mis && !m.phys.table) m.phys = PhysArgs{h->mt.mis_ref.p, nullptr, h->n_mis_ref};
+    m.tab = h->sv.n_mats <= RTG_LDS_MATS && h->sv.n_lights <= RTG_LDS_LIGHTS && m.phys.n <= RTG_LDS_PHYS;
+    return m;
+}
+
+static int launch_shade_bounce(const ShadeMode& m, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
+                               const PathBufs& p, int b) {
+    switch (m.family) {
+    case ShadeFamily::Pick: return launch_shade_pick(m, grid, st, s, a, p, b);
+    case ShadeFamily::Phys: return launch_shade_phys(m, grid, st, s, a, p, b);
+    case ShadeFamily::Mis: return launch_shade_mis(m, grid, st, s, a, p, b);
+    case ShadeFamily::Trans:
+    case ShadeFamily::TransMis: return launch_shade_trans(m, grid, st, s, a, p, b);
+    default: return launch_shade(m, grid, st, s, a, p, b);
+    }
+}
+
 // Pixel list in tile order (32x32 tiles, row-major inside a tile), for the requested tiles.
 int set_pixels(rtg_handle* h, const uint32_t* tiles, uint32_t n_tiles) {
     const int TS = 32;
@@ -587,6 +631,7 @@ static int issue_chunk(rtg_handle* h, ChunkSlot& sl, const ChunkArgs& a, int max
                        unsigned long long* d_wt, std::vector<int>& kinds) {
     const hipStream_t ss = sl.stream;
     const PathBufs& pb = sl.pb;
+    const ShadeMode mode = shade_mode_of(h);
     int rc;
     TraceIO io{};
     io.stats = h->d_stats;
@@ -616,20 +661,7 @@ static int issue_chunk(rtg_handle* h, ChunkSlot& sl, const ChunkArgs& a, int max
             if ((rc = shade_tiles(h, a, b, hostgrid, tiles))) return rc;
             if (tiles) {
                 timed_begin(h, ss, kinds.size());
-                const bool tab = h->sv.n_mats <= RTG_LDS_MATS && h->sv.n_lights <= RTG_LDS_LIGHTS;
-                const bool alt = h->integrator != RTG_INTEGRATOR_PATH;
-                const EnvTable et = env_table_of(h);  // RTG_ENV_LUMINANCE with a table: k_shade_env
-                const LightPick pk = light_pick_of(h);  // RTG_LIGHTS_POWER with a table: k_shade_pick
-                const PhysArgs ph = phys_args_of(h);  // RTG_MATERIALS_PHYSICAL with such a material: k_shade_phys
-                if (trans_active(h))  // ... with a rough dielectric record: k_shade_trans / k_shade_trans_mis
-                    rc = launch_shade_trans(h, alt, tab && ph.n <= RTG_LDS_PHYS, 8 * tiles, ss, a, pb, b - 1, et, pk, ph);
-                else if (path_mis_active(h))  // RTG_PATH_MIS_POWER under PATH: k_shade_mis
-                    rc = launch_shade_mis(h, tab, 8 * tiles, ss, a, pb, b - 1, et, pk, ph);
-                else if (ph.table)
-                    rc = launch_shade_phys(alt, tab && ph.n <= RTG_LDS_PHYS, 8 * tiles, ss, h->sv, a, pb, b - 1, et, pk, ph);
-                else if (pk.table) rc = launch_shade_pick(alt, tab, 8 * tiles, ss, h->sv, a, pb, b - 1, et, pk);
-                else rc = launch_shade(alt, tab, 8 * tiles, ss, h->sv, a, pb, b - 1, &et);
-                if (rc) return rc;
+                if ((rc = launch_shade_bounce(mode, 8 * tiles, ss, h->sv, a, pb, b - 1))) return rc;
                 timed_end(h, ss, kinds, 2);
             }
         }
@@ -828,9 +860,7 @@ int rtg_camera_sampling_defaults(rtg_camera_sampling* p) {
 int rtg_set_camera_sampling(rtg_handle* h, const rtg_camera_sampling* p) {
     if (!h) { g_err = "rtg_set_camera_sampling: null handle"; return RTG_ERR_ARG; }
     if (int rc = camera_sampling_check("rtg_set_camera_sampling", p)) return rc;
-    HIPOK(hipSetDevice(h->device));
-    if (int rc = join_frames(h)) return rc;  // queued calls render with the settings they were queued under
-    HIPOK(hipStreamSynchronize(h->stream));
+    if (int rc = settle(h)) return rc;
     h->cam_sampling = *p;
     return RTG_OK;
 }
@@ -853,30 +883,12 @@ int rtg_probe_camera_samples(rtg_handle* h, const uint32_t* pixels, const uint32
         }
     if (n == 0) return RTG_OK;
     HIPOK(hipSetDevice(h->device));
-    unsigned *d_pix = nullptr, *d_smp = nullptr;
-    float *d_rays = nullptr, *d_xy = nullptr;
-    auto run = [&]() -> int {
-        HIPOK(hipMalloc((void**)&d_pix, (size_t)n * sizeof(unsigned)));
-        HIPOK(hipMalloc((void**)&d_smp, (size_t)n * sizeof(unsigned)));
-        HIPOK(hipMalloc((void**)&d_rays, (size_t)n * 8 * sizeof(float)));
-        HIPOK(hipMalloc((void**)&d_xy, (size_t)n * 2 * sizeof(float)));
-        HIPOK(hipMemcpy(d_pix, pixels, (size_t)n * sizeof(unsigned), hipMemcpyHostToDevice));
-        HIPOK(hipMemcpy(d_smp, samples, (size_t)n * sizeof(unsigned), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_probe_camera, dim3((n + 255) / 256), dim3(256), 0, nullptr, h->cam, cam_sampling_dev(h),
-                           (unsigned long long)seed, (const unsigned*)d_pix, (const unsigned*)d_smp, (unsigned)n, d_rays,
-                           d_xy);
-        HIPOK(hipGetLastError());
-        HIPOK(hipDeviceSynchronize());
-        HIPOK(hipMemcpy(rays, d_rays, (size_t)n * 8 * sizeof(float), hipMemcpyDeviceToHost));
-        if (film_xy) HIPOK(hipMemcpy(film_xy, d_xy, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost));
-        return RTG_OK;
-    };
-    const int rc = run();
-    (void)hipFree(d_pix);
-    (void)hipFree(d_smp);
-    (void)hipFree(d_rays);
-    (void)hipFree(d_xy);
-    return rc;
+    return probe_run({{pixels, (size_t)n * sizeof(unsigned)}, {samples, (size_t)n * sizeof(unsigned)}},
+                     {{rays, (size_t)n * 8 * sizeof(float)}, {film_xy, (size_t)n * 2 * sizeof(float)}}, [&](void* const* d) {
+                         hipLaunchKernelGGL(k_probe_camera, dim3((n + 255) / 256), dim3(256), 0, nullptr, h->cam,
+                                            cam_sampling_dev(h), (unsigned long long)seed, (const unsigned*)d[0],
+                                            (const unsigned*)d[1], (unsigned)n, (float*)d[2], (float*)d[3]);
+                     });
 }
 
 int rtg_render_async(rtg_handle* h, uint32_t first, uint32_t n, uint64_t seed, const uint32_t* tiles,

@@ -45,14 +45,15 @@ __global__ __launch_bounds__(RTG_TB, ALT ? RTG_SHADE_ENV_ALT_WAVES : RTG_SHADE_W
 }
 
 
-// The launch of one shading bounce (render_impl): the pathTrace-only kernel or the one holding every
-// per-pixel estimator, with or without the LDS material / light tables; env with a table: k_shade_env.
-int launch_shade(bool alt, bool tab, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
-                 const PathBufs& p, int b, const EnvTable* env) {
-    if (env && env->table) {  // RTG_ENV_LUMINANCE with a table (PATH, DIRECT, DIRECT_MIS)
+// The launch of one shading bounce (ShadeFamily::Plain and Env): the pathTrace-only kernel or the one
+// holding every per-pixel estimator, with or without the LDS material / light tables.
+int launch_shade(const ShadeMode& m, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
+                 const PathBufs& p, int b) {
+    const bool alt = m.alt, tab = m.tab;
+    if (m.family == ShadeFamily::Env) {  // RTG_ENV_LUMINANCE with a table (PATH, DIRECT, DIRECT_MIS)
         auto kenv = alt ? (tab ? k_shade_env<true, true> : k_shade_env<true, false>)
                         : (tab ? k_shade_env<false, true> : k_shade_env<false, false>);
-        hipLaunchKernelGGL(kenv, dim3(grid), dim3(RTG_TB), 0, st, s, a, p, b, *env);
+        hipLaunchKernelGGL(kenv, dim3(grid), dim3(RTG_TB), 0, st, s, a, p, b, m.env);
         LAUNCH_OK("k_shade_env");
         return RTG_OK;
     }

@@ -51,18 +51,10 @@ __global__ void k_probe_env_pdf(EnvTable et, const float* dirs, unsigned n, floa
     pdf[i] = et.table ? env_pdf_luminance(et, d) : uniform_sphere_pdf();
 }
 
-bool path_mis_active(const rtg_handle* h) {
-    return h->path_mis == RTG_PATH_MIS_POWER && h->integrator == RTG_INTEGRATOR_PATH && h->d_mis_index != nullptr;
-}
-
-int launch_shade_mis(const rtg_handle* h, bool tab, unsigned grid, hipStream_t st, const ChunkArgs& a, const PathBufs& p,
-                     int b, const EnvTable& env, const LightPick& pick, const PhysArgs& phys) {
-    // the reference model, or a scene without a physical record: reference-kind records for every index
-    const PhysArgs ph = phys.table ? phys : PhysArgs{h->d_mis_ref, nullptr, h->n_mis_ref};
-    const MisArgs mis{h->d_mis_index};
-    const bool t = tab && ph.n <= RTG_LDS_PHYS;
-    hipLaunchKernelGGL(t ? k_shade_mis<true> : k_shade_mis<false>, dim3(grid), dim3(RTG_TB), 0, st, h->sv, a, p, b,
-                       env.table, pick, ph.table, ph.n, mis);
+int launch_shade_mis(const ShadeMode& m, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
+                     const PathBufs& p, int b) {
+    hipLaunchKernelGGL(m.tab ? k_shade_mis<true> : k_shade_mis<false>, dim3(grid), dim3(RTG_TB), 0, st, s, a, p, b,
+                       m.env.table, m.pick, m.phys.table, m.phys.n, m.mis);
     LAUNCH_OK("k_shade_mis");
     return RTG_OK;
 }
@@ -86,55 +78,18 @@ static int build_mis_tables(rtg_handle* h) {
     const int n_ref = have && h->n_phys > 0 ? h->n_phys : 1;
     PhysMat zero;
     std::memset(&zero, 0, sizeof(zero));  // tag RTG_MODEL_REFERENCE: nothing else of it is read
-    uint2* d_ix = nullptr;
-    PhysMat* d_ref = nullptr;
-    auto run = [&]() -> int {
-        int rc;
-        if ((rc = dev_upload(&d_ix, ix))) return rc;
-        return dev_upload(&d_ref, std::vector<PhysMat>((size_t)n_ref, zero));
-    };
-    const int rc = run();
-    if (rc != RTG_OK) {
-        (void)hipFree(d_ix);
-        (void)hipFree(d_ref);
-        return rc;
-    }
-    (void)hipFree(h->d_mis_index);
-    (void)hipFree(h->d_mis_ref);
-    h->d_mis_index = d_ix;
-    h->d_mis_ref = d_ref;
+    DevBuf<uint2> d_ix;
+    DevBuf<PhysMat> d_ref;
+    if (int rc = d_ix.upload(ix)) return rc;
+    if (int rc = d_ref.upload(std::vector<PhysMat>((size_t)n_ref, zero))) return rc;
+    h->mt.mis_index = std::move(d_ix);
+    h->mt.mis_ref = std::move(d_ref);
     h->n_mis_ref = n_ref;
     h->light_of.swap(of);
     return RTG_OK;
 }
 
-int mis_sync_tables(rtg_handle* h) { return h->d_mis_index ? build_mis_tables(h) : (int)RTG_OK; }
-
-// device buffers for a probe of n inputs of `in_floats` floats each and one float out
-static int probe_run(const float* in0, const float* in1, size_t in_floats, uint32_t n, float* out,
-                     void (*launch)(const float*, const float*, unsigned, float*, const void*), const void* ctx) {
-    float *d0 = nullptr, *d1 = nullptr, *d_out = nullptr;
-    auto run = [&]() -> int {
-        HIPOK(hipMalloc((void**)&d0, (size_t)n * in_floats * sizeof(float)));
-        HIPOK(hipMemcpy(d0, in0, (size_t)n * in_floats * sizeof(float), hipMemcpyHostToDevice));
-        if (in1) {
-            HIPOK(hipMalloc((void**)&d1, (size_t)n * in_floats * sizeof(float)));
-            HIPOK(hipMemcpy(d1, in1, (size_t)n * in_floats * sizeof(float), hipMemcpyHostToDevice));
-        }
-        HIPOK(hipMalloc((void**)&d_out, (size_t)n * sizeof(float)));
-        (void)hipGetLastError();  // (a stale error of other code on this thread is not this launch's)
-        launch(d0, d1, (unsigned)n, d_out, ctx);
-        HIPOK(hipGetLastError());
-        HIPOK(hipDeviceSynchronize());
-        HIPOK(hipMemcpy(out, d_out, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-        return RTG_OK;
-    };
-    const int rc = run();
-    (void)hipFree(d0);
-    (void)hipFree(d1);
-    (void)hipFree(d_out);
-    return rc;
-}
+int mis_sync_tables(rtg_handle* h) { return h->mt.mis_index.p ? build_mis_tables(h) : (int)RTG_OK; }
 
 extern "C" {
 
@@ -149,10 +104,8 @@ int rtg_path_mis_check(int mode) {
 int rtg_set_path_mis(rtg_handle* h, int mode) {
     if (!h) { g_err = "rtg_set_path_mis: null handle"; return RTG_ERR_ARG; }
     if (int rc = rtg_path_mis_check(mode)) return rc;
-    HIPOK(hipSetDevice(h->device));
-    if (int rc = join_frames(h)) return rc;  // queued calls render with the settings they were queued under
-    HIPOK(hipStreamSynchronize(h->stream));
-    if (mode == RTG_PATH_MIS_POWER && !h->d_mis_index)
+    if (int rc = settle(h)) return rc;
+    if (mode == RTG_PATH_MIS_POWER && !h->mt.mis_index.p)
         if (int rc = build_mis_tables(h)) return rc;
     h->path_mis = mode;
     return RTG_OK;
@@ -166,7 +119,7 @@ int rtg_get_path_mis(rtg_handle* h, int* mode) {
 
 int rtg_light_of_triangle(rtg_handle* h, int32_t* out) {
     if (!h || !out) { g_err = "rtg_light_of_triangle: null argument"; return RTG_ERR_ARG; }
-    if (!h->d_mis_index) { g_err = "rtg_light_of_triangle: the map is built by the first RTG_PATH_MIS_POWER setting"; return RTG_ERR_ARG; }
+    if (!h->mt.mis_index.p) { g_err = "rtg_light_of_triangle: the map is built by the first RTG_PATH_MIS_POWER setting"; return RTG_ERR_ARG; }
     std::memcpy(out, h->light_of.data(), h->light_of.size() * sizeof(int32_t));
     return RTG_OK;
 }
@@ -175,11 +128,11 @@ int rtg_probe_mis_weight(const float* p, const float* q, uint32_t n, float* w) {
     if (!p || !q || !w) { g_err = "rtg_probe_mis_weight: null argument"; return RTG_ERR_ARG; }
     if (n > 0x7fffffffu / 4u) { g_err = "rtg_probe_mis_weight: too many cases"; return RTG_ERR_ARG; }
     if (n == 0) return RTG_OK;
-    return probe_run(p, q, 1, n, w,
-                     [](const float* a, const float* b, unsigned m, float* o, const void*) {
-                         hipLaunchKernelGGL(k_probe_mis_weight, dim3((m + 255) / 256), dim3(256), 0, nullptr, a, b, m, o);
-                     },
-                     nullptr);
+    const size_t bytes = (size_t)n * sizeof(float);
+    return probe_run({{p, bytes}, {q, bytes}}, {{w, bytes}}, [&](void* const* d) {
+        hipLaunchKernelGGL(k_probe_mis_weight, dim3((n + 255) / 256), dim3(256), 0, nullptr, (const float*)d[0],
+                           (const float*)d[1], (unsigned)n, (float*)d[2]);
+    });
 }
 
 int rtg_probe_env_pdf(rtg_handle* h, const float* dirs, uint32_t n, float* pdf) {
@@ -187,16 +140,10 @@ int rtg_probe_env_pdf(rtg_handle* h, const float* dirs, uint32_t n, float* pdf) 
     if (n > 0x7fffffffu / 12u) { g_err = "rtg_probe_env_pdf: too many cases"; return RTG_ERR_ARG; }
     if (n == 0) return RTG_OK;
     HIPOK(hipSetDevice(h->device));
-    // the table under the handle's setting, whatever its integrator (as rtg_probe_env_samples)
-    const bool lum = h->env_mode == RTG_ENV_LUMINANCE && h->d_env_table != nullptr;
-    const unsigned w = (unsigned)h->sv.env_w, hh = (unsigned)h->sv.env_h;
-    const EnvTable et = lum ? EnvTable{h->d_env_table, w * hh, w, hh} : EnvTable{nullptr, 0u, 0u, 0u};
-    return probe_run(dirs, nullptr, 3, n, pdf,
-                     [](const float* a, const float*, unsigned m, float* o, const void* ctx) {
-                         hipLaunchKernelGGL(k_probe_env_pdf, dim3((m + 255) / 256), dim3(256), 0, nullptr,
-                                            *static_cast<const EnvTable*>(ctx), a, m, o);
-                     },
-                     &et);
+    return probe_run({{dirs, (size_t)n * 3 * sizeof(float)}}, {{pdf, (size_t)n * sizeof(float)}}, [&](void* const* d) {
+        hipLaunchKernelGGL(k_probe_env_pdf, dim3((n + 255) / 256), dim3(256), 0, nullptr, env_table_set(h),
+                           (const float*)d[0], (unsigned)n, (float*)d[1]);
+    });
 }
 
 }  // extern "C"

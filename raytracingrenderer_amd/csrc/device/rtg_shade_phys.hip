@@ -57,19 +57,13 @@ __global__ void k_probe_material(const float* in, int n, float* out) {
     o[13] = o[14] = o[15] = 0.0f;
 }
 
-int launch_shade_phys(bool alt, bool tab, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
-                      const PathBufs& p, int b, const EnvTable& env, const LightPick& pick, const PhysArgs& phys) {
-    auto kern = alt ? (tab ? k_shade_phys<true, true> : k_shade_phys<true, false>)
-                    : (tab ? k_shade_phys<false, true> : k_shade_phys<false, false>);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(RTG_TB), 0, st, s, a, p, b, env, pick, phys);
+int launch_shade_phys(const ShadeMode& m, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
+                      const PathBufs& p, int b) {
+    auto kern = m.alt ? (m.tab ? k_shade_phys<true, true> : k_shade_phys<true, false>)
+                      : (m.tab ? k_shade_phys<false, true> : k_shade_phys<false, false>);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(RTG_TB), 0, st, s, a, p, b, m.env, m.pick, m.phys);
     LAUNCH_OK("k_shade_phys");
     return RTG_OK;
-}
-
-PhysArgs phys_args_of(const rtg_handle* h) {
-    const bool on = h->material_model == RTG_MATERIALS_PHYSICAL && h->phys_built && h->phys_any &&
-                    (h->integrator == RTG_INTEGRATOR_PATH || h->integrator == RTG_INTEGRATOR_DIRECT);
-    return on ? PhysArgs{h->d_phys, h->d_phys_index, h->n_phys} : PhysArgs{nullptr, nullptr, 0};
 }
 
 static bool param_ok(float x) { return x >= 0.0f && x <= RTG_FLT_MAX; }  // (false for NaN)
@@ -127,23 +121,12 @@ static int build_phys_table(rtg_handle* h) {
         any = any || h->mat_params[h->tri_mat[t]].model != RTG_MODEL_REFERENCE;
         any_trans = any_trans || h->mat_params[h->tri_mat[t]].model == RTG_MODEL_ROUGH_DIELECTRIC;
     }
-    PhysMat* d_tab = nullptr;
-    unsigned* d_idx = nullptr;
-    auto run = [&]() -> int {
-        int rc;
-        if ((rc = dev_upload(&d_tab, uniq))) return rc;
-        return dev_upload(&d_idx, index);
-    };
-    const int rc = run();
-    if (rc != RTG_OK) {
-        (void)hipFree(d_tab);
-        (void)hipFree(d_idx);
-        return rc;
-    }
-    (void)hipFree(h->d_phys);
-    (void)hipFree(h->d_phys_index);
-    h->d_phys = d_tab;
-    h->d_phys_index = d_idx;
+    DevBuf<PhysMat> d_tab;
+    DevBuf<unsigned> d_idx;
+    if (int rc = d_tab.upload(uniq)) return rc;
+    if (int rc = d_idx.upload(index)) return rc;
+    h->mt.phys = std::move(d_tab);
+    h->mt.phys_index = std::move(d_idx);
     h->n_phys = (int)uniq.size();
     h->phys_any = any;
     h->trans_any = any_trans;
@@ -161,9 +144,7 @@ int rtg_material_params_check(const rtg_material_params* params, uint32_t n, uin
 int rtg_set_material_params(rtg_handle* h, const rtg_material_params* params, uint32_t n) {
     if (!h) { g_err = "rtg_set_material_params: null handle"; return RTG_ERR_ARG; }
     if (int rc = material_params_check("rtg_set_material_params", params, n, h->n_desc_mats)) return rc;
-    HIPOK(hipSetDevice(h->device));
-    if (int rc = join_frames(h)) return rc;  // queued calls render with the settings they were queued under
-    HIPOK(hipStreamSynchronize(h->stream));
+    if (int rc = settle(h)) return rc;
     std::vector<rtg_material_params> prev(params, params + n);
     prev.swap(h->mat_params);
     h->phys_built = false;
@@ -191,9 +172,7 @@ int rtg_set_material_model(rtg_handle* h, int mode) {
         g_err = "rtg_set_material_model: the scene has no materials";
         return RTG_ERR_ARG;
     }
-    HIPOK(hipSetDevice(h->device));
-    if (int rc = join_frames(h)) return rc;
-    HIPOK(hipStreamSynchronize(h->stream));
+    if (int rc = settle(h)) return rc;
     if (mode == RTG_MATERIALS_PHYSICAL && !h->phys_built)
         if (int rc = build_phys_table(h)) return rc;
     h->material_model = mode;
@@ -217,23 +196,10 @@ int rtg_probe_material(const float* cases, uint32_t n, float* out) {
         }
     }
     if (n == 0) return RTG_OK;
-    float *d_in = nullptr, *d_out = nullptr;
-    auto run = [&]() -> int {
-        HIPOK(hipMalloc((void**)&d_in, (size_t)n * 28 * sizeof(float)));
-        HIPOK(hipMalloc((void**)&d_out, (size_t)n * 16 * sizeof(float)));
-        HIPOK(hipMemcpy(d_in, cases, (size_t)n * 28 * sizeof(float), hipMemcpyHostToDevice));
-        (void)hipGetLastError();  // (a stale error of other code on this thread is not this launch's)
-        hipLaunchKernelGGL(k_probe_material, dim3((n + 255) / 256), dim3(256), 0, nullptr, (const float*)d_in, (int)n,
-                           d_out);
-        HIPOK(hipGetLastError());
-        HIPOK(hipDeviceSynchronize());
-        HIPOK(hipMemcpy(out, d_out, (size_t)n * 16 * sizeof(float), hipMemcpyDeviceToHost));
-        return RTG_OK;
-    };
-    const int rc = run();
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return rc;
+    return probe_run({{cases, (size_t)n * 28 * sizeof(float)}}, {{out, (size_t)n * 16 * sizeof(float)}}, [&](void* const* d) {
+        hipLaunchKernelGGL(k_probe_material, dim3((n + 255) / 256), dim3(256), 0, nullptr, (const float*)d[0], (int)n,
+                           (float*)d[1]);
+    });
 }
 
 }  // extern "C"

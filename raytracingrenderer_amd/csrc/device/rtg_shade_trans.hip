@@ -2,7 +2,7 @@
 // RTG_MODEL_ROUGH_DIELECTRIC; rtg_trans.h has the model). k_shade_trans is k_shade_phys, and
 // k_shade_trans_mis is k_shade_mis, with a record of that tag shaded by the model's reflection and
 // transmission lobes; conductor, plastic and Oren-Nayar records shade as they do there, so a scene can
-// mix all models. render_impl launches the family only under RTG_MATERIALS_PHYSICAL with PATH or DIRECT
+// mix all models. shade_mode_of chooses the family only under RTG_MATERIALS_PHYSICAL with PATH or DIRECT
 // and a triangle that uses such a record. Built with rtg_shade.hip's flags
 // (raytracingrenderer_amd/build.py: DEVICE_FLAGS).
 #include "rtg_internal.h"
@@ -75,23 +75,17 @@ __global__ void k_probe_transmission(const float* in, int n, float* out) {
     o[13] = o[14] = o[15] = 0.0f;
 }
 
-bool trans_active(const rtg_handle* h) {
-    return h->material_model == RTG_MATERIALS_PHYSICAL && h->phys_built && h->trans_any &&
-           (h->integrator == RTG_INTEGRATOR_PATH || h->integrator == RTG_INTEGRATOR_DIRECT);
-}
-
-int launch_shade_trans(const rtg_handle* h, bool alt, bool tab, unsigned grid, hipStream_t st, const ChunkArgs& a,
-                       const PathBufs& p, int b, const EnvTable& env, const LightPick& pick, const PhysArgs& phys) {
-    if (path_mis_active(h)) {
-        const MisArgs mis{h->d_mis_index};
-        hipLaunchKernelGGL(tab ? k_shade_trans_mis<true> : k_shade_trans_mis<false>, dim3(grid), dim3(RTG_TB), 0, st,
-                           h->sv, a, p, b, env.table, pick, phys.table, phys.n, mis);
+int launch_shade_trans(const ShadeMode& m, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
+                       const PathBufs& p, int b) {
+    if (m.family == ShadeFamily::TransMis) {
+        hipLaunchKernelGGL(m.tab ? k_shade_trans_mis<true> : k_shade_trans_mis<false>, dim3(grid), dim3(RTG_TB), 0, st, s,
+                           a, p, b, m.env.table, m.pick, m.phys.table, m.phys.n, m.mis);
         LAUNCH_OK("k_shade_trans_mis");
         return RTG_OK;
     }
-    auto kern = alt ? (tab ? k_shade_trans<true, true> : k_shade_trans<true, false>)
-                    : (tab ? k_shade_trans<false, true> : k_shade_trans<false, false>);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(RTG_TB), 0, st, h->sv, a, p, b, env, pick, phys);
+    auto kern = m.alt ? (m.tab ? k_shade_trans<true, true> : k_shade_trans<true, false>)
+                      : (m.tab ? k_shade_trans<false, true> : k_shade_trans<false, false>);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(RTG_TB), 0, st, s, a, p, b, m.env, m.pick, m.phys);
     LAUNCH_OK("k_shade_trans");
     return RTG_OK;
 }
@@ -108,23 +102,10 @@ int rtg_probe_transmission(const float* cases, uint32_t n, float* out) {
         }
     }
     if (n == 0) return RTG_OK;
-    float *d_in = nullptr, *d_out = nullptr;
-    auto run = [&]() -> int {
-        HIPOK(hipMalloc((void**)&d_in, (size_t)n * 28 * sizeof(float)));
-        HIPOK(hipMalloc((void**)&d_out, (size_t)n * 16 * sizeof(float)));
-        HIPOK(hipMemcpy(d_in, cases, (size_t)n * 28 * sizeof(float), hipMemcpyHostToDevice));
-        (void)hipGetLastError();  // (a stale error of other code on this thread is not this launch's)
-        hipLaunchKernelGGL(k_probe_transmission, dim3((n + 255) / 256), dim3(256), 0, nullptr, (const float*)d_in, (int)n,
-                           d_out);
-        HIPOK(hipGetLastError());
-        HIPOK(hipDeviceSynchronize());
-        HIPOK(hipMemcpy(out, d_out, (size_t)n * 16 * sizeof(float), hipMemcpyDeviceToHost));
-        return RTG_OK;
-    };
-    const int rc = run();
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return rc;
+    return probe_run({{cases, (size_t)n * 28 * sizeof(float)}}, {{out, (size_t)n * 16 * sizeof(float)}}, [&](void* const* d) {
+        hipLaunchKernelGGL(k_probe_transmission, dim3((n + 255) / 256), dim3(256), 0, nullptr, (const float*)d[0], (int)n,
+                           (float*)d[1]);
+    });
 }
 
 }  // extern "C"

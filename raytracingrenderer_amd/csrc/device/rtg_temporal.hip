@@ -302,9 +302,7 @@ int rtg_temporal_check(const rtg_temporal_params* p) { return temporal_check("rt
 int rtg_geometry_guide(rtg_handle* h, float* pos_t, float* normal_id) {
     if (!h) { g_err = "rtg_geometry_guide: null handle"; return RTG_ERR_ARG; }
     if (int rc = check_size("rtg_geometry_guide", h)) return rc;
-    HIPOK(hipSetDevice(h->device));
-    if (int rc = join_frames(h)) return rc;
-    HIPOK(hipStreamSynchronize(h->stream));  // slot 0's buffers are free
+    if (int rc = settle(h)) return rc;  // slot 0's buffers are free
     if (int rc = ensure_state(h)) return rc;
     TemporalState& t = *h->tp;
     const float4* g = nullptr;
@@ -330,9 +328,7 @@ int rtg_temporal_accumulate(rtg_handle* h, const rtg_temporal_params* p, float* 
     if (int rc = temporal_check("rtg_temporal_accumulate", p)) return rc;
     if (h->spp == 0) { g_err = "rtg_temporal_accumulate: the film holds no samples (spp == 0)"; return RTG_ERR_ARG; }
     if (int rc = check_size("rtg_temporal_accumulate", h)) return rc;
-    HIPOK(hipSetDevice(h->device));
-    if (int rc = join_frames(h)) return rc;  // the film holds every queued frame first
-    HIPOK(hipStreamSynchronize(h->stream));  // slot 0's buffers are free
+    if (int rc = settle(h)) return rc;  // the film holds every queued frame, and slot 0's buffers are free
     if (int rc = ensure_state(h)) return rc;
     TemporalState& t = *h->tp;
     TemporalArgs a{};

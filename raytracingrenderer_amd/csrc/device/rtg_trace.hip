@@ -636,17 +636,12 @@ int capture_begin(rtg_handle* h, TraceIO& io, unsigned seg_tiles, hipStream_t ss
 static int trace_query(rtg_handle* h, const float* rays, uint32_t n, float* hits, int32_t* vis, bool any) {
     if (!h || !rays || (!hits && !vis)) return RTG_ERR_ARG;
     if (n == 0) return RTG_OK;
-    HIPOK(hipSetDevice(h->device));
-    if (int rc = join_frames(h)) return rc;
-    HIPOK(hipStreamSynchronize(h->stream));  // slot 0's overflow stack is free (hipMemcpy below)
+    int rc = settle(h);  // slot 0's overflow stack is free
+    if (rc) return rc;
     // path-id indirection of the trace kernels: identity queue over n query rays
-    float4 *d_o = nullptr, *d_d = nullptr;
-    unsigned* d_q = nullptr;
-    void* d_out = nullptr;
-    HIPOK(hipMalloc((void**)&d_o, (size_t)n * sizeof(float4)));
-    HIPOK(hipMalloc((void**)&d_d, (size_t)n * sizeof(float4)));
-    HIPOK(hipMalloc((void**)&d_q, (size_t)n * sizeof(unsigned)));
-    HIPOK(hipMalloc(&d_out, (size_t)n * (any ? sizeof(int) : sizeof(float4))));
+    DevBuf<float4> d_o, d_d;
+    DevBuf<unsigned> d_q;
+    DevBuf<char> d_out;
     {
         std::vector<float4> vo(n), vd(n);
         std::vector<unsigned> q(n);
@@ -656,14 +651,12 @@ static int trace_query(rtg_handle* h, const float* rays, uint32_t n, float* hits
             vd[i] = make_float4(r[4], r[5], r[6], 0.0f);
             q[i] = i;
         }
-        HIPOK(hipMemcpy(d_o, vo.data(), (size_t)n * sizeof(float4), hipMemcpyHostToDevice));
-        HIPOK(hipMemcpy(d_d, vd.data(), (size_t)n * sizeof(float4), hipMemcpyHostToDevice));
-        HIPOK(hipMemcpy(d_q, q.data(), (size_t)n * sizeof(unsigned), hipMemcpyHostToDevice));
+        if ((rc = d_o.upload(vo)) || (rc = d_d.upload(vd)) || (rc = d_q.upload(q))) return rc;
     }
+    if ((rc = d_out.alloc((size_t)n * (any ? sizeof(int) : sizeof(float4))))) return rc;
     unsigned hc[4] = {n, 0, 0, 0};
     HIPOK(hipMemcpy(h->d_qctr, hc, sizeof(hc), hipMemcpyHostToDevice));
-    int rc = ensure_ovf(h, h->slot[0]);
-    if (rc) return rc;
+    if ((rc = ensure_ovf(h, h->slot[0]))) return rc;
     if (h->slot[0].stream) HIPOK(hipStreamSynchronize(h->slot[0].stream));
     TraceIO io{};
     io.fetch = h->d_qctr + 1;
@@ -672,26 +665,22 @@ static int trace_query(rtg_handle* h, const float* rays, uint32_t n, float* hits
     io.cull = h->cull;
     io.wide = h->wide;
     if (any) {
-        io.squeue = d_q;
-        io.sray_o = d_o;
-        io.sray_d = d_d;
+        io.squeue = d_q.p;
+        io.sray_o = d_o.p;
+        io.sray_d = d_d.p;
         io.scount = h->d_qctr;
-        io.visible = (int*)d_out;
+        io.visible = (int*)d_out.p;
     } else {
-        io.queue = d_q;
-        io.ray_o = d_o;
-        io.ray_d = d_d;
+        io.queue = d_q.p;
+        io.ray_o = d_o.p;
+        io.ray_d = d_d.p;
         io.count = h->d_qctr;
-        io.hits = (float4*)d_out;
+        io.hits = (float4*)d_out.p;
     }
     if ((rc = launch_trace(h, io, h->stream))) return rc;
     HIPOK(hipStreamSynchronize(h->stream));
-    if (any) HIPOK(hipMemcpy(vis, d_out, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-    else HIPOK(hipMemcpy(hits, d_out, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost));
-    (void)hipFree(d_o);
-    (void)hipFree(d_d);
-    (void)hipFree(d_q);
-    (void)hipFree(d_out);
+    if (any) HIPOK(hipMemcpy(vis, d_out.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    else HIPOK(hipMemcpy(hits, d_out.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost));
     return RTG_OK;
 }
 

@@ -1,40 +1,14 @@
 """Register budget of the denoiser's kernels (compiled here for gfx950, no GPU needed): none of the
 kernels of rtg_denoise.hip may spill or use scratch memory (a scratch reload per tap is a vector-
 memory request in a loop that is all vector-memory requests)."""
-import os
-import re
-import subprocess
-import tempfile
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEVICE = os.path.join(ROOT, "raytracingrenderer_amd", "csrc", "device")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-UNIT = "device/rtg_denoise.hip"
+import kernel_meta
 
 
 @pytest.fixture(scope="module")
 def kernels():
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    from raytracingrenderer_amd.build import DEVICE_FLAGS, DEVICE_SRC  # the unit with the flags the build uses
-    assert UNIT in DEVICE_SRC
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "k.s")
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"] +
-                       DEVICE_FLAGS.get(UNIT, []) + ["--cuda-device-only", "-S", "-o", out,
-                                                     os.path.join(DEVICE, os.path.basename(UNIT))],
-                       check=True, capture_output=True)
-        s = open(out).read()
-    res = {}
-    md = s[s.index("amdhsa.kernels"):]
-    for blk in md.split("  - .agpr_count")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        res[name] = {k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1))
-                     for k in ("vgpr_count", "vgpr_spill_count", "sgpr_count", "sgpr_spill_count",
-                               "private_segment_fixed_size", "group_segment_fixed_size")}
-    return res
+    return kernel_meta.kernels("device/rtg_denoise.hip")
 
 
 def test_every_denoise_kernel_is_found(kernels):

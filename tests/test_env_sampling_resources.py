@@ -2,16 +2,9 @@
 RTG_ENV_LUMINANCE lives in kernels of its own (k_shade_env, rtg_shade.hip), so the default's k_shade
 instantiations must come out of the compiler as they did before it existed, and the new kernels (and
 rtg_env.hip's) must hold their state in registers."""
-import os
-import re
-import subprocess
-import tempfile
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEVICE = os.path.join(ROOT, "raytracingrenderer_amd", "csrc", "device")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+import kernel_meta
 
 # The figures of the commit before k_shade_env (DESIGN.md §8c), same flags: (VGPRs, SGPRs, LDS bytes,
 # spilled VGPRs). k_shade<true, *> spilled then as it does now; it is pinned so that it gets no worse.
@@ -25,26 +18,7 @@ BEFORE = {
 
 @pytest.fixture(scope="module")
 def kernels():
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    from raytracingrenderer_amd.build import DEVICE_CXXFLAGS, DEVICE_FLAGS, DEVICE_SRC
-    assert "device/rtg_env.hip" in DEVICE_SRC
-    res = {}
-    for rel in ("device/rtg_shade.hip", "device/rtg_env.hip"):
-        with tempfile.TemporaryDirectory() as d:
-            out = os.path.join(d, "k.s")
-            flags = [f for f in DEVICE_CXXFLAGS if f != "-fPIC"]
-            subprocess.run([HIPCC, "--offload-arch=gfx950"] + flags + DEVICE_FLAGS.get(rel, []) +
-                           ["--cuda-device-only", "-S", "-o", out, os.path.join(DEVICE, os.path.basename(rel))],
-                           check=True, capture_output=True)
-            s = open(out).read()
-        md = s[s.index("amdhsa.kernels"):]
-        for blk in md.split("  - .agpr_count")[1:]:
-            name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-            res[name] = {k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1))
-                         for k in ("vgpr_count", "vgpr_spill_count", "sgpr_count", "sgpr_spill_count",
-                                   "private_segment_fixed_size", "group_segment_fixed_size")}
-    return res
+    return kernel_meta.kernels("device/rtg_shade.hip", "device/rtg_env.hip")
 
 
 def _find(kernels, prefix):

@@ -1,39 +1,17 @@
 """Register budget of the hot kernels (compiled here for gfx950, no GPU needed): a change that
 makes the traversal or shading kernel spill in its loop costs ~15 % (a scratch reload per node
 step is a vector-memory request in a request-bound loop), so the spill counts are pinned."""
-import os
-import re
-import subprocess
-import tempfile
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEVICE = os.path.join(ROOT, "raytracingrenderer_amd", "csrc", "device")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+import kernel_meta
+
+UNITS = ("device/rtg_trace.hip", "device/rtg_shade.hip")
 
 
 @pytest.fixture(scope="module")
 def kernels():
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    from raytracingrenderer_amd.build import DEVICE_FLAGS  # each unit with the flags the build uses
-    res = {"_asm": {}}
-    for rel in ("device/rtg_trace.hip", "device/rtg_shade.hip"):
-        with tempfile.TemporaryDirectory() as d:
-            out = os.path.join(d, "k.s")
-            subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"] +
-                           DEVICE_FLAGS.get(rel, []) + ["--cuda-device-only", "-S", "-o", out,
-                                                        os.path.join(DEVICE, os.path.basename(rel))],
-                           check=True, capture_output=True)
-            s = open(out).read()
-        res["_asm"][rel] = s
-        md = s[s.index("amdhsa.kernels"):]
-        for blk in md.split("  - .agpr_count")[1:]:
-            name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-            res[name] = {k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1))
-                         for k in ("vgpr_count", "vgpr_spill_count", "sgpr_count", "sgpr_spill_count",
-                                   "private_segment_fixed_size", "group_segment_fixed_size")}
+    res = kernel_meta.kernels(*UNITS)
+    res["_asm"] = {rel: kernel_meta.asm(rel) for rel in UNITS}
     return res
 
 

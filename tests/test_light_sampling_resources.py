@@ -2,16 +2,9 @@
 RTG_LIGHTS_POWER lives in kernels of its own (k_shade_pick, rtg_light_pick.hip), so the default's
 k_shade and k_shade_env instantiations must be no larger than on the commit before it, and the new
 kernels must hold their state in registers (DESIGN.md §8d has the table)."""
-import os
-import re
-import subprocess
-import tempfile
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEVICE = os.path.join(ROOT, "raytracingrenderer_amd", "csrc", "device")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+import kernel_meta
 
 # The figures of the commit before k_shade_pick, same flags, compiled once: (VGPRs, SGPRs, LDS bytes,
 # spilled VGPRs, spilled SGPRs, scratch bytes). k_shade<true, *> spilled then as it does now.
@@ -31,30 +24,9 @@ KEYS = ("vgpr_count", "sgpr_count", "group_segment_fixed_size", "vgpr_spill_coun
 
 @pytest.fixture(scope="module")
 def kernels():
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    from raytracingrenderer_amd.build import DEVICE_CXXFLAGS, DEVICE_FLAGS, DEVICE_SRC
-    assert "device/rtg_light_pick.hip" in DEVICE_SRC
+    from raytracingrenderer_amd.build import DEVICE_FLAGS
     assert DEVICE_FLAGS["device/rtg_light_pick.hip"] == DEVICE_FLAGS["device/rtg_shade.hip"]
-    res = {}
-    procs = []
-    with tempfile.TemporaryDirectory() as d:
-        for rel in ("device/rtg_shade.hip", "device/rtg_light_pick.hip"):
-            out = os.path.join(d, os.path.basename(rel) + ".s")
-            flags = [f for f in DEVICE_CXXFLAGS if f != "-fPIC"]
-            procs.append((out, subprocess.Popen([HIPCC, "--offload-arch=gfx950"] + flags + DEVICE_FLAGS.get(rel, []) +
-                                                ["--cuda-device-only", "-S", "-o", out,
-                                                 os.path.join(DEVICE, os.path.basename(rel))],
-                                                stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
-        for out, pr in procs:
-            log = pr.communicate()[0]
-            assert pr.returncode == 0, log.decode(errors="replace")
-            s = open(out).read()
-            md = s[s.index("amdhsa.kernels"):]
-            for blk in md.split("  - .agpr_count")[1:]:
-                name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-                res[name] = {k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1)) for k in KEYS}
-    return res
+    return kernel_meta.kernels("device/rtg_shade.hip", "device/rtg_light_pick.hip")
 
 
 def _find(kernels, prefix):

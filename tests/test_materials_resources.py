@@ -2,16 +2,9 @@
 RTG_MATERIALS_PHYSICAL lives in kernels of its own (k_shade_phys, rtg_shade_phys.hip), so the sixteen
 existing k_shade / k_shade_env / k_shade_pick instantiations must be no larger than DESIGN.md 8c / 8d
 record them, and the new kernels must hold their state in registers (DESIGN.md 8e has the table)."""
-import os
-import re
-import subprocess
-import tempfile
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEVICE = os.path.join(ROOT, "raytracingrenderer_amd", "csrc", "device")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+import kernel_meta
 
 KEYS = ("vgpr_count", "sgpr_count", "group_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count",
         "private_segment_fixed_size")
@@ -46,30 +39,9 @@ PHYS = {
 
 @pytest.fixture(scope="module")
 def kernels():
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    from raytracingrenderer_amd.build import DEVICE_CXXFLAGS, DEVICE_FLAGS, DEVICE_SRC
-    assert "device/rtg_shade_phys.hip" in DEVICE_SRC
+    from raytracingrenderer_amd.build import DEVICE_FLAGS
     assert DEVICE_FLAGS["device/rtg_shade_phys.hip"] == DEVICE_FLAGS["device/rtg_shade.hip"]
-    res = {}
-    procs = []
-    with tempfile.TemporaryDirectory() as d:
-        for rel in ("device/rtg_shade.hip", "device/rtg_light_pick.hip", "device/rtg_shade_phys.hip"):
-            out = os.path.join(d, os.path.basename(rel) + ".s")
-            flags = [f for f in DEVICE_CXXFLAGS if f != "-fPIC"]
-            procs.append((out, subprocess.Popen([HIPCC, "--offload-arch=gfx950"] + flags + DEVICE_FLAGS.get(rel, []) +
-                                                ["--cuda-device-only", "-S", "-o", out,
-                                                 os.path.join(DEVICE, os.path.basename(rel))],
-                                                stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
-        for out, pr in procs:
-            log = pr.communicate()[0]
-            assert pr.returncode == 0, log.decode(errors="replace")
-            s = open(out).read()
-            md = s[s.index("amdhsa.kernels"):]
-            for blk in md.split("  - .agpr_count")[1:]:
-                name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-                res[name] = {k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1)) for k in KEYS}
-    return res
+    return kernel_meta.kernels("device/rtg_shade.hip", "device/rtg_light_pick.hip", "device/rtg_shade_phys.hip")
 
 
 def _find(kernels, prefix):

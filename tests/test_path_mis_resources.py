@@ -2,16 +2,9 @@
 lives in kernels of its own (k_shade_mis, rtg_shade_mis.hip), which must hold their state in registers at
 the six waves per SIMD they are bounded for (DESIGN.md 8f has the table). The twenty existing shading
 kernels are pinned by tests/test_materials_resources.py, which compiles the units they live in."""
-import os
-import re
-import subprocess
-import tempfile
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEVICE = os.path.join(ROOT, "raytracingrenderer_amd", "csrc", "device")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+import kernel_meta
 
 KEYS = ("vgpr_count", "sgpr_count", "group_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count",
         "private_segment_fixed_size")
@@ -26,27 +19,10 @@ MIS = {
 
 @pytest.fixture(scope="module")
 def kernels():
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    from raytracingrenderer_amd.build import DEVICE_CXXFLAGS, DEVICE_FLAGS, DEVICE_SRC
+    from raytracingrenderer_amd.build import DEVICE_FLAGS
     rel = "device/rtg_shade_mis.hip"
-    assert rel in DEVICE_SRC
     assert DEVICE_FLAGS[rel] == DEVICE_FLAGS["device/rtg_shade.hip"]
-    res = {}
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "rtg_shade_mis.s")
-        flags = [f for f in DEVICE_CXXFLAGS if f != "-fPIC"]
-        pr = subprocess.run([HIPCC, "--offload-arch=gfx950"] + flags + DEVICE_FLAGS[rel] +
-                            ["--cuda-device-only", "-S", "-o", out, os.path.join(DEVICE, os.path.basename(rel))],
-                            stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-        assert pr.returncode == 0, pr.stdout.decode(errors="replace")
-        s = open(out).read()
-        md = s[s.index("amdhsa.kernels"):]
-        for blk in md.split("  - .agpr_count")[1:]:
-            name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-            res[name] = {k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1)) for k in KEYS}
-            res[name]["max_flat_workgroup_size"] = int(re.search(r"\.max_flat_workgroup_size:\s+(\d+)", blk).group(1))
-    return res
+    return kernel_meta.kernels(rel)
 
 
 def _find(kernels, prefix):

@@ -3,16 +3,9 @@ lives in a unit of its own (rtg_shade_trans.hip) built with rtg_shade.hip's flag
 registers at its launch bound of six waves per SIMD, is no larger than DESIGN.md 8g records, and carries
 none of the pinned families' names (tests/test_materials_resources.py and tests/test_path_mis_resources.py
 count those)."""
-import os
-import re
-import subprocess
-import tempfile
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEVICE = os.path.join(ROOT, "raytracingrenderer_amd", "csrc", "device")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+import kernel_meta
 
 KEYS = ("vgpr_count", "sgpr_count", "group_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count",
         "private_segment_fixed_size")
@@ -30,27 +23,10 @@ TRANS = {
 
 @pytest.fixture(scope="module")
 def kernels():
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    from raytracingrenderer_amd.build import DEVICE_CXXFLAGS, DEVICE_FLAGS, DEVICE_SRC
+    from raytracingrenderer_amd.build import DEVICE_FLAGS
     rel = "device/rtg_shade_trans.hip"
-    assert rel in DEVICE_SRC
     assert DEVICE_FLAGS[rel] == DEVICE_FLAGS["device/rtg_shade.hip"]
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "rtg_shade_trans.s")
-        flags = [f for f in DEVICE_CXXFLAGS if f != "-fPIC"]
-        r = subprocess.run([HIPCC, "--offload-arch=gfx950"] + flags + DEVICE_FLAGS[rel] +
-                           ["--cuda-device-only", "-S", "-o", out, os.path.join(DEVICE, os.path.basename(rel))],
-                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-        assert r.returncode == 0, r.stdout.decode(errors="replace")
-        s = open(out).read()
-    res = {}
-    md = s[s.index("amdhsa.kernels"):]
-    for blk in md.split("  - .agpr_count")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        res[name] = {k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1)) for k in KEYS}
-        res[name]["max_flat_workgroup_size"] = int(re.search(r"\.max_flat_workgroup_size:\s+(\d+)", blk).group(1))
-    return res
+    return kernel_meta.kernels(rel)
 
 
 def test_the_unit_holds_the_family_and_its_probe(kernels):

@@ -739,8 +739,8 @@ int  rtg_get_camera(rtg_handle* h, rtg_camera* cam, rtg_camera_proj* proj);
  * rtg_temporal_history copies H (w*h*4; RTG_ERR_ARG before the first accumulate); rtg_temporal_copy_device the
  * last result (w*h*3 floats, device to device); rtg_temporal_ms the device time of the last call's guide pass
  * (0 when none ran) and of its k_temporal launch. Not covered: miss pixels after a move (the background is not
- * reprojected: they restart), groups (rtg_group_set_camera only), chaining into rtg_denoise on the device,
- * variance-guided weights, moving geometry. */
+ * reprojected: they restart), groups (rtg_group_set_camera only), moving geometry. Chaining into an a-trous
+ * filter on the device with variance-guided weights is rtg_svgf_accumulate, below. */
 typedef struct rtg_temporal_params {
     float max_history, plane_tolerance, normal_cos;
 } rtg_temporal_params;
@@ -752,6 +752,74 @@ int  rtg_temporal_history(rtg_handle* h, float* rgb_len /* w*h*4 */);
 int  rtg_temporal_copy_device(rtg_handle* h, void* dst_device);
 int  rtg_temporal_reset(rtg_handle* h);
 int  rtg_temporal_ms(rtg_handle* h, double* guide_ms, double* accumulate_ms);
+
+/* ---- variance-guided filtering of the temporal history (SVGF, Schied et al. 2017; DESIGN.md §8j;
+ * rtg_svgf.hip, tests/svgf_ref.py restates it in numpy). rtg_svgf_accumulate advances the same per-handle
+ * history H = {rgb, len}, history camera and guide as rtg_temporal_accumulate, keeps next to it a moments
+ * history M = {mu1, mu2} (8 B per pixel, a ping-pong pair like H), and filters the new H with K a-trous levels
+ * whose luminance term is scaled by a per-pixel variance. After any sequence of svgf calls rtg_temporal_history
+ * returns the bits the same sequence of rtg_temporal_accumulate calls would have left. A
+ * rtg_temporal_accumulate call invalidates M only: the next svgf call starts M from its frame and continues H.
+ * rtg_temporal_reset drops both. The albedo / shading-normal guides are the denoiser's cached ones (dropped by
+ * rtg_set_camera, rendered again on demand). The film, Film::SPP, the integrator, the options and the
+ * statistics are left as they were.
+ * IEEE float32 with one rounding per operation, no contraction; sums in the order written, taps in
+ * (dy outer, dx inner) order. L(c) = (0.2126f r + 0.7152f g) + 0.0722f b. cur = film / (float)spp per channel,
+ * m = (float)spp, l = L(cur), s = l l.
+ *   1. temporal + moments   have, the admitted taps, their weights w, sw, n, a = m / (n + m), the output rgb and
+ *        len are exactly those of rtg_temporal_accumulate (no history / camera unchanged / camera moved). With a
+ *        history: hmu_k = (sum of w M[q].k) / sw over the same admitted taps in the same order; camera unchanged:
+ *        M[p] itself. mu_k = hmu_k + (x - hmu_k) a, x = l for k = 1 and x = s for k = 2. Without a history, or
+ *        with M invalid: mu1 = l, mu2 = s.
+ *   2. variance   vt = mu2 - mu1 mu1, clamped as vt > 0 ? vt : 0. If len >= min_history, v = vt. Otherwise over
+ *        the 7x7 window, dy, dx in -3..3, taps inside the image: the centre is always admitted; another tap q is
+ *        admitted if p and q are both misses in the current guide, or both hits with
+ *        fabsf(dot(X_q - X_p, Ng_p)) <= plane_tolerance t_p and fabsf(dot(Ng_q, Ng_p)) >= normal_cos (the two
+ *        tests of rtg_temporal_accumulate on the *current* guide; with the camera unchanged that is the history's
+ *        own). Admitted: c0 += 1, c1 += mu1_q, c2 += mu2_q. e1 = c1 / c0, vs = c2 / c0 - e1 e1, clamped at 0 as
+ *        above; v = vs (min_history / len). v goes into the .w of the colour record {rgb, v}.
+ *   3. filter   `iterations` levels, level i at step = 1 << i, the 5x5 B3 taps h of rtg_denoise. Per pixel p
+ *        first gv = sum over the 3x3 neighbourhood at step 1, coordinates clamped to the image, of
+ *        (k(dy) k(dx)) v_q with k = {0.25f, 0.5f, 0.25f}, and
+ *        il = 1.0f / ((sigma_luminance sigma_luminance) gv + variance_floor). Per tap q inside the image:
+ *        w = h[dy] h[dx]; luminance: dl = L(c_q) - L(c_p), t = 1 - (dl dl) il, clamped as t > 0 ? t : 0,
+ *        w = w (t t); albedo (when sigma_albedo > 0) and shading normal with normal_squarings: rtg_denoise's two
+ *        terms, "both background -> 1" included; plane, a hard test on the current geometry guide: both hits
+ *        need fabsf(dot(X_q - X_p, Ng_p)) <= plane_tolerance t_p, else w = 0; a hit and a miss give w = 0; two
+ *        misses pass; the centre tap passes by definition. sw += w, acc += w c_q.rgb, av += (w w) v_q. Out: if
+ *        sw > 0, rgb = acc / sw and v = av / (sw sw); otherwise the centre's record is kept. No sigma is halved
+ *        per level: the filtered variance does that job.
+ * The result is the rgb of the last level; rtg_svgf_variance returns step 2's v (w*h), rtg_svgf_moments the new
+ * M (w*h*2), rtg_svgf_copy_device the last result (w*h*3 floats, device to device). It is not a NaN filter:
+ * non-finite values spread as the definition says. Parameters: temporal as rtg_temporal_accumulate;
+ * iterations 1..RTG_DENOISE_MAX_ITERATIONS; normal_squarings 0..8; sigma_luminance > 0 finite; sigma_albedo
+ * <= 0 off, else finite >= 1e-6; min_history > 0 finite; variance_floor > 0 finite. Anything else, a NaN
+ * included, is RTG_ERR_ARG before any device call (rtg_svgf_check is that check alone, no device needed);
+ * spp == 0 is RTG_ERR_ARG; a read-back before the first accumulate is RTG_ERR_ARG. A failed call leaves the
+ * state and the film as they were. The defaults (64, 0.01f, 0.9f; 5, 5, 4, 0.1f, 4, 1e-8f) are choices, not
+ * measured optima. The whole chain (guide pass if the camera moved, guides if dropped, temporal + moments,
+ * variance, a copy of the guide's positions, the levels, unpack) is queued on the handle's stream with no host
+ * wait in between; the call returns when the result is in the handle's device buffer, and in out when given.
+ * rtg_svgf_ms gives the device time of the last call's guide pass (0 when none ran), temporal + moments
+ * kernel, variance kernel and all filter levels together (the copy of the positions included). Not covered:
+ * albedo demodulation, feeding level 0's output back into the history, one first-hit pass for all three
+ * guides, groups, the CLI, integration/rtg_rtbase.h, reprojecting the background, moving geometry. */
+typedef struct rtg_svgf_params {
+    rtg_temporal_params temporal;   /* max_history, plane_tolerance, normal_cos: as rtg_temporal_accumulate */
+    uint32_t iterations;            /* 1..RTG_DENOISE_MAX_ITERATIONS, default 5 */
+    uint32_t normal_squarings;      /* 0..8, default 5: the shading-normal term of rtg_denoise */
+    float sigma_luminance;          /* > 0 finite, default 4 */
+    float sigma_albedo;             /* <= 0 off, else finite >= 1e-6, default 0.1 (rtg_denoise's rule) */
+    float min_history;              /* > 0 finite, default 4: below it the variance is estimated spatially */
+    float variance_floor;           /* > 0 finite, default 1e-8 */
+} rtg_svgf_params;
+int  rtg_svgf_defaults(rtg_svgf_params* p);  /* 64, 0.01f, 0.9f; 5, 5, 4.0f, 0.1f, 4.0f, 1e-8f */
+int  rtg_svgf_check(const rtg_svgf_params* p);
+int  rtg_svgf_accumulate(rtg_handle* h, const rtg_svgf_params* p, float* out /* w*h*3 or NULL */);
+int  rtg_svgf_variance(rtg_handle* h, float* var /* w*h */);
+int  rtg_svgf_moments(rtg_handle* h, float* mu /* w*h*2 */);
+int  rtg_svgf_copy_device(rtg_handle* h, void* dst_device);
+int  rtg_svgf_ms(rtg_handle* h, double* guide_ms, double* accumulate_ms, double* variance_ms, double* filter_ms);
 
 /* Add samples [first_sample, first_sample+n_samples) of every pixel in the listed 32x32 tiles
  * (tile id = ty*tilesX + tx, RTBase TILE_SIZE=32; tile_ids=NULL = all tiles) to the film, in

@@ -96,6 +96,12 @@ class rtg_temporal_params(C.Structure):
     _fields_ = [("max_history", C.c_float), ("plane_tolerance", C.c_float), ("normal_cos", C.c_float)]
 
 
+class rtg_svgf_params(C.Structure):
+    _fields_ = [("temporal", rtg_temporal_params), ("iterations", C.c_uint32), ("normal_squarings", C.c_uint32),
+                ("sigma_luminance", C.c_float), ("sigma_albedo", C.c_float), ("min_history", C.c_float),
+                ("variance_floor", C.c_float)]
+
+
 class rth_load_options(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("skip_missing", C.c_int32),
                 ("bvh_threads", C.c_int32), ("envmap", C.c_char_p)]
@@ -226,6 +232,14 @@ RTG_EXPORTS = [
     ("rtg_temporal_copy_device", C.c_int, [C.c_void_p, C.c_void_p]),
     ("rtg_temporal_reset", C.c_int, [C.c_void_p]),
     ("rtg_temporal_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    # variance-guided filtering of the temporal history (rtg_svgf.hip)
+    ("rtg_svgf_defaults", C.c_int, [C.POINTER(rtg_svgf_params)]),
+    ("rtg_svgf_check", C.c_int, [C.POINTER(rtg_svgf_params)]),
+    ("rtg_svgf_accumulate", C.c_int, [C.c_void_p, C.POINTER(rtg_svgf_params), f32p]),
+    ("rtg_svgf_variance", C.c_int, [C.c_void_p, f32p]),
+    ("rtg_svgf_moments", C.c_int, [C.c_void_p, f32p]),
+    ("rtg_svgf_copy_device", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("rtg_svgf_ms", C.c_int, [C.c_void_p] + [C.POINTER(C.c_double)] * 4),
 ]
 
 RTH_EXPORTS = [

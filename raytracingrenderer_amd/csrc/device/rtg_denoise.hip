@@ -21,7 +21,7 @@
 // 64 consecutive x of one row: every tap of a wave is a contiguous row segment at any step, and
 // the row tests are wave-uniform. One launch per iteration on the handle's stream, no host wait
 // in between. No address depends on a pixel value.
-#include "rtg_internal.h"
+#include "rtg_filter_state.h"
 
 #include <cmath>
 
@@ -133,18 +133,6 @@ __global__ __launch_bounds__(256) void k_dn_atrous(DenoiseArgs a) {
 }
 
 // ------------------------------------------------------------------ host side
-struct DenoiseState {
-    size_t n = 0;                  // pixels the buffers hold
-    float4* col[2] = {nullptr, nullptr};
-    float4* guide = nullptr;       // packed guides (valid when guides_ready)
-    float* albedo = nullptr;       // the guide films as rendered (rtg_denoise_guides)
-    float* normal = nullptr;
-    float* out = nullptr;          // last result, tightly packed rgb
-    bool guides_ready = false, have_result = false;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    double ms = 0.0;
-};
-
 int denoise_check_params(const char* who, const rtg_denoise_params* p) {
     auto bad = [&](const char* what) {
         g_err = std::string(who) + ": " + what;
@@ -247,11 +235,13 @@ static int ensure_state(rtg_handle* h) {
     return alloc_bufs(*h->dn, (size_t)h->W * h->H);
 }
 
+int denoise_state(rtg_handle* h) { return ensure_state(h); }
+
 // The guides, once per handle: 1 sample of the albedo and of the shading-normal integrator into
 // scratch films (the film swap of rtg_render_adaptive), every tile, then packed. Both estimators
 // stop at the first hit and draw no random number, so the seed and the sample index do not matter.
 // The film, Film::SPP, the integrator, the options and the statistics are left as they were.
-static int ensure_guides(rtg_handle* h) {
+int ensure_guides(rtg_handle* h, bool wait) {
     DenoiseState& d = *h->dn;
     if (d.guides_ready) return RTG_OK;
     const size_t nf = d.n * 3 * sizeof(float);
@@ -287,7 +277,7 @@ static int ensure_guides(rtg_handle* h) {
     h->launch_rays = keep_rays;
     if (rc) return rc;
     if ((rc = pack_guides(d, h->stream))) return rc;
-    HIPOK(hipStreamSynchronize(h->stream));
+    if (wait) HIPOK(hipStreamSynchronize(h->stream));  // otherwise the caller's own wait on h's stream covers them
     d.guides_ready = true;
     return RTG_OK;
 }

@@ -18,16 +18,10 @@
 // film's three floats and at most 4 x 3 tap loads; it writes one history record and three floats.
 // Blocks are 64 x 4 pixels with a wave on 64 consecutive x of one row, as k_dn_atrous lays them out.
 // No atomics; no address depends on a colour (the tap addresses depend on geometry alone).
-#include "rtg_internal.h"
+#include "rtg_filter_state.h"
 
 #include <cmath>
 #include <cstring>
-
-struct TemporalProj {  // the history camera's projectOntoCamera state
-    float P[16];       // projectionMatrix
-    float C2V[16];     // cameraToView
-    float W, H;
-};
 
 struct TemporalArgs {
     const float* film;     // the film's sums, 3 floats per pixel
@@ -164,26 +158,13 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
 }
 
 // ------------------------------------------------------------------ host side
-struct TemporalState {
-    size_t n = 0;                           // pixels the buffers hold
-    float4* hist[2] = {nullptr, nullptr};   // hist[cur] is H
-    int cur = 0;
-    float4* hguide = nullptr;               // the history camera's guide (valid when have_hist)
-    float4* cguide = nullptr;               // the guide cache (valid for ccam / cproj when cache_ready)
-    float* out = nullptr;                   // last result, tightly packed rgb
-    bool have_hist = false, cache_ready = false, have_result = false;
-    DevCamera hcam{}, ccam{};
-    rtg_camera_proj hproj{}, cproj{};
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    double guide_ms = 0.0, accumulate_ms = 0.0;
-};
-
 void temporal_release(rtg_handle* h) {
     TemporalState* t = h->tp;
     if (!t) return;
     (void)hipFree(t->hist[0]); (void)hipFree(t->hist[1]); (void)hipFree(t->hguide);
     (void)hipFree(t->cguide); (void)hipFree(t->out);
     for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
+    svgf_release(*t);
     delete t;
     h->tp = nullptr;
 }
@@ -212,7 +193,7 @@ static int ensure_state(rtg_handle* h) {
     return RTG_OK;
 }
 
-static bool same_camera(const DevCamera& a, const rtg_camera_proj& ap, const DevCamera& b, const rtg_camera_proj& bp) {
+bool same_camera(const DevCamera& a, const rtg_camera_proj& ap, const DevCamera& b, const rtg_camera_proj& bp) {
     return std::memcmp(&a, &b, sizeof(DevCamera)) == 0 && std::memcmp(&ap, &bp, sizeof(rtg_camera_proj)) == 0;
 }
 
@@ -222,7 +203,7 @@ static bool same_camera(const DevCamera& a, const rtg_camera_proj& ap, const Dev
 // camera pass of rtg_render_instant_radiosity), then k_geometry_guide. The caller has joined the queued
 // frames and waited for the stream (slot 0's buffers are free). The options, the statistics and the film
 // are not touched: no counting kernels, no tally, no film write.
-static int current_guide(rtg_handle* h, const float4** guide, bool* traced) {
+int current_guide(rtg_handle* h, const float4** guide, bool* traced) {
     TemporalState& t = *h->tp;
     *traced = false;
     if (t.have_hist && same_camera(h->cam, h->proj, t.hcam, t.hproj)) { *guide = t.hguide; return RTG_OK; }
@@ -275,7 +256,30 @@ static int current_guide(rtg_handle* h, const float4** guide, bool* traced) {
     return RTG_OK;
 }
 
-static int temporal_check(const char* who, const rtg_temporal_params* p) {
+int temporal_state(const char* who, rtg_handle* h) {
+    if (int rc = check_size(who, h)) return rc;
+    return ensure_state(h);
+}
+
+void temporal_advance(rtg_handle* h, bool unchanged, const float4* g) {
+    TemporalState& t = *h->tp;
+    t.cur ^= 1;
+    if (!unchanged) {  // the stored camera and guide become the current ones
+        if (g == t.cguide) {
+            // the cache's buffer becomes the history's; the history's old guide stays cached under its camera
+            std::swap(t.hguide, t.cguide);
+            const bool was = t.have_hist;
+            t.ccam = t.hcam;
+            t.cproj = t.hproj;
+            t.cache_ready = was;
+        }
+        t.hcam = h->cam;
+        t.hproj = h->proj;
+        t.have_hist = true;
+    }
+}
+
+int temporal_check(const char* who, const rtg_temporal_params* p) {
     auto bad = [&](const char* what) {
         g_err = std::string(who) + ": " + what;
         return RTG_ERR_ARG;
@@ -371,20 +375,8 @@ int rtg_temporal_accumulate(rtg_handle* h, const rtg_temporal_params* p, float* 
     float ms = 0.0f;
     t.guide_ms = (traced && hipEventElapsedTime(&ms, t.ev[0], t.ev[1]) == hipSuccess) ? ms : 0.0;
     if (hipEventElapsedTime(&ms, t.ev[2], t.ev[3]) == hipSuccess) t.accumulate_ms = ms;
-    t.cur ^= 1;
-    if (!unchanged) {  // the stored camera and guide become the current ones
-        if (g == t.cguide) {
-            // the cache's buffer becomes the history's; the history's old guide stays cached under its camera
-            std::swap(t.hguide, t.cguide);
-            const bool was = t.have_hist;
-            t.ccam = t.hcam;
-            t.cproj = t.hproj;
-            t.cache_ready = was;
-        }
-        t.hcam = h->cam;
-        t.hproj = h->proj;
-        t.have_hist = true;
-    }
+    temporal_advance(h, unchanged, g);
+    if (t.sv) t.sv->mom_valid = false;  // the moments history of rtg_svgf_accumulate no longer belongs to H
     t.have_result = true;
     return RTG_OK;
 }

@@ -166,6 +166,30 @@ def temporal_defaults():
     return {"max_history": p.max_history, "plane_tolerance": p.plane_tolerance, "normal_cos": p.normal_cos}
 
 
+def _svgf_params(max_history, plane_tolerance, normal_cos, iterations, normal_squarings, sigma_luminance,
+                 sigma_albedo, min_history, variance_floor):
+    return N.rtg_svgf_params(_temporal_params(max_history, plane_tolerance, normal_cos), int(iterations),
+                             int(normal_squarings), float(sigma_luminance), float(sigma_albedo), float(min_history),
+                             float(variance_floor))
+
+
+def svgf_check(max_history=64.0, plane_tolerance=0.01, normal_cos=0.9, iterations=5, normal_squarings=5,
+               sigma_luminance=4.0, sigma_albedo=0.1, min_history=4.0, variance_floor=1e-8):
+    """rtg_svgf_check: the argument check of RayTracer.svgf alone (no device needed)."""
+    p = _svgf_params(max_history, plane_tolerance, normal_cos, iterations, normal_squarings, sigma_luminance,
+                     sigma_albedo, min_history, variance_floor)
+    _check(N.rtg().rtg_svgf_check(C.byref(p)), N.rtg().rtg_last_error)
+
+
+def svgf_defaults():
+    p = N.rtg_svgf_params()
+    _check(N.rtg().rtg_svgf_defaults(C.byref(p)), N.rtg().rtg_last_error)
+    return {"max_history": p.temporal.max_history, "plane_tolerance": p.temporal.plane_tolerance,
+            "normal_cos": p.temporal.normal_cos, "iterations": p.iterations, "normal_squarings": p.normal_squarings,
+            "sigma_luminance": p.sigma_luminance, "sigma_albedo": p.sigma_albedo, "min_history": p.min_history,
+            "variance_floor": p.variance_floor}
+
+
 def write_synthetic_scene(out_dir, n_tris=1_000_000, seed=20251015, width=1024, height=1024):
     """C3 synthetic scene as .gem + scene.json + albedo.png + env.hdr."""
     os.makedirs(out_dir, exist_ok=True)
@@ -510,6 +534,42 @@ class RayTracer:
         g, a = C.c_double(), C.c_double()
         _check(self._lib.rtg_temporal_ms(self._h, C.byref(g), C.byref(a)), self._lib.rtg_last_error)
         return g.value, a.value
+
+    def svgf(self, max_history=64.0, plane_tolerance=0.01, normal_cos=0.9, iterations=5, normal_squarings=5,
+             sigma_luminance=4.0, sigma_albedo=0.1, min_history=4.0, variance_floor=1e-8):
+        """Variance-guided filtering of the temporal history (rtg_svgf_accumulate): temporal()'s step on the
+        same history, a moments history next to it, a per-pixel variance (spatial below min_history) and
+        `iterations` a-trous levels whose luminance term that variance scales, all on the device. The loop is:
+        move, clear(), render(), svgf(). Returns the (H, W, 3) float32 image; the film, SPP and the settings
+        stay as they were. Waits for queued frames first."""
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        p = _svgf_params(max_history, plane_tolerance, normal_cos, iterations, normal_squarings, sigma_luminance,
+                         sigma_albedo, min_history, variance_floor)
+        _check(self._lib.rtg_svgf_accumulate(self._h, C.byref(p), N.ptr(out, C.c_float)), self._lib.rtg_last_error)
+        return out
+
+    def svgf_variance(self):
+        """The variance the last svgf() fed to its first level, (H, W) float32."""
+        out = np.zeros((self.height, self.width), np.float32)
+        _check(self._lib.rtg_svgf_variance(self._h, N.ptr(out, C.c_float)), self._lib.rtg_last_error)
+        return out
+
+    def svgf_moments(self):
+        """The moments history, (H, W, 2) float32: the first two moments of the luminance."""
+        out = np.zeros((self.height, self.width, 2), np.float32)
+        _check(self._lib.rtg_svgf_moments(self._h, N.ptr(out, C.c_float)), self._lib.rtg_last_error)
+        return out
+
+    def copy_svgf_to(self, device_ptr):
+        """The last svgf() result, (H, W, 3) float32, copied to device memory on this GPU."""
+        _check(self._lib.rtg_svgf_copy_device(self._h, C.c_void_p(device_ptr)), self._lib.rtg_last_error)
+
+    def svgf_ms(self):
+        """(guide_ms, accumulate_ms, variance_ms, filter_ms): device time of the last svgf()'s guide pass (0
+        when none ran), temporal + moments kernel, variance kernel and filter levels together."""
+        v = [C.c_double() for _ in range(4)]
+        _check(self._lib.rtg_svgf_ms(self._h, *[C.byref(x) for x in v]), self._lib.rtg_last_error)
+        return tuple(x.value for x in v)
 
     def set_camera_sampling(self, filter="none", filter_radius=None, lens_radius=0.0, focal_distance=1.0):
         """Anti-aliasing and depth of field (rtg_set_camera_sampling). filter "none" (default: every

@@ -45,7 +45,8 @@ extern "C" {
  *    rtg_*_material_model, rtg_*_material_params and rtg_probe_material; path-tracer MIS,
  *    rtg_*_path_mis, rtg_probe_mis_weight, rtg_probe_env_pdf and rtg_light_of_triangle; rough dielectric
  *    transmission, RTG_MODEL_ROUGH_DIELECTRIC and rtg_probe_transmission; a movable camera, rtg_*_camera;
- *    the geometry guide and temporal accumulation, rtg_geometry_guide and rtg_temporal_*) */
+ *    the geometry guide and temporal accumulation, rtg_geometry_guide and rtg_temporal_*; the G-buffer,
+ *    rtg_gbuffer and rtg_gbuffer_ms) */
 #define RTG_ABI_VERSION 6
 
 /* error codes */
@@ -797,13 +798,12 @@ int  rtg_temporal_ms(rtg_handle* h, double* guide_ms, double* accumulate_ms);
  * included, is RTG_ERR_ARG before any device call (rtg_svgf_check is that check alone, no device needed);
  * spp == 0 is RTG_ERR_ARG; a read-back before the first accumulate is RTG_ERR_ARG. A failed call leaves the
  * state and the film as they were. The defaults (64, 0.01f, 0.9f; 5, 5, 4, 0.1f, 4, 1e-8f) are choices, not
- * measured optima. The whole chain (guide pass if the camera moved, guides if dropped, temporal + moments,
+ * measured optima. The whole chain (the fused first-hit pass of rtg_gbuffer if a guide is missing, temporal + moments,
  * variance, a copy of the guide's positions, the levels, unpack) is queued on the handle's stream with no host
  * wait in between; the call returns when the result is in the handle's device buffer, and in out when given.
  * rtg_svgf_ms gives the device time of the last call's guide pass (0 when none ran), temporal + moments
  * kernel, variance kernel and all filter levels together (the copy of the positions included). Not covered:
- * albedo demodulation, feeding level 0's output back into the history, one first-hit pass for all three
- * guides, groups, the CLI, integration/rtg_rtbase.h, reprojecting the background, moving geometry. */
+ * albedo demodulation, feeding level 0's output back into the history, groups, the CLI, integration/rtg_rtbase.h, reprojecting the background, moving geometry. */
 typedef struct rtg_svgf_params {
     rtg_temporal_params temporal;   /* max_history, plane_tolerance, normal_cos: as rtg_temporal_accumulate */
     uint32_t iterations;            /* 1..RTG_DENOISE_MAX_ITERATIONS, default 5 */
@@ -820,6 +820,38 @@ int  rtg_svgf_variance(rtg_handle* h, float* var /* w*h */);
 int  rtg_svgf_moments(rtg_handle* h, float* mu /* w*h*2 */);
 int  rtg_svgf_copy_device(rtg_handle* h, void* dst_device);
 int  rtg_svgf_ms(rtg_handle* h, double* guide_ms, double* accumulate_ms, double* variance_ms, double* filter_ms);
+
+/* ---- the G-buffer: one first-hit pass for the geometry guide and the albedo / shading-normal guides (DESIGN.md
+ * §8k; rtg_gbuffer.hip). The pinhole ray through every pixel centre (whatever rtg_set_camera_sampling says) is
+ * traced once by the existing generate and traversal kernels; one kernel, k_gbuffer, then writes per pixel from
+ * its closest hit (t, id, alpha, beta), gamma = 1 - (alpha + beta):
+ *   pos_t, normal_id   the two records of rtg_geometry_guide, word for word.
+ *   shading_normal     what 1 sample of RTG_INTEGRATOR_NORMALS leaves in a cleared film, i.e. the second output of
+ *                      rtg_denoise_guides: sn = normalize(n0 alpha + n1 beta + n2 gamma) of the vertex normals,
+ *                      negated when the material is two-sided and dot(-d, sn) < 0; the value is
+ *                      0 + fabsf(sn) per component; a miss: 0.
+ *   albedo             what 1 sample of RTG_INTEGRATOR_ALBEDO leaves in a cleared film, i.e. the first output of
+ *                      rtg_denoise_guides: an emitter gives its emission; otherwise a = the material's texture at
+ *                      (u, v) interpolated as the normals are (Texture::sample), and a mirror gives a, glass 0,
+ *                      every other kind a / (float)M_PI; a miss gives the environment map in direction d
+ *                      (EnvironmentMap::evaluate), 0 without one; each as 0 + c per component.
+ * Neither integrator draws a random number, so the seed, the sample index, the integrator, the material model
+ * and the light, environment, camera and path sampling modes do not reach any output.
+ * rtg_gbuffer fills the temporal state's guide cache (rtg_geometry_guide, rtg_temporal_accumulate and
+ * rtg_svgf_accumulate pick it up) and the denoiser's cached guides (rtg_denoise, rtg_denoise_guides,
+ * rtg_group_denoise and rtg_svgf_accumulate pick them up), and marks both valid for the handle's camera: after
+ * it none of those calls traces a camera ray until rtg_set_camera drops the guides. When both are already at
+ * hand it runs nothing. rtg_svgf_accumulate runs the same pass in place of a guide pass and two renders. The
+ * calls that need only one kind keep their own, cheaper or documented, path when they have to produce it
+ * themselves. The film, Film::SPP, the integrator, the options, the statistics and the camera-sampling setting
+ * are left as they were. The call issues and waits for queued frames first, queues the pass on the handle's
+ * stream with no host wait, waits once and copies out what was asked for: any output may be NULL.
+ * rtg_gbuffer_ms gives the device time of the pass (generate, traversal, k_gbuffer) in the last rtg_gbuffer or
+ * rtg_svgf_accumulate call, 0 when the caches served it. Not covered: motion vectors, groups,
+ * integration/rtg_rtbase.h, switching rtg_denoise to this pass. */
+int  rtg_gbuffer(rtg_handle* h, float* pos_t /* w*h*4 */, float* normal_id /* w*h*4 */, float* albedo /* w*h*3 */,
+                 float* shading_normal /* w*h*3 */);
+int  rtg_gbuffer_ms(rtg_handle* h, double* ms);
 
 /* Add samples [first_sample, first_sample+n_samples) of every pixel in the listed 32x32 tiles
  * (tile id = ty*tilesX + tx, RTBase TILE_SIZE=32; tile_ids=NULL = all tiles) to the film, in

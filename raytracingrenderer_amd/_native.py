@@ -240,6 +240,9 @@ RTG_EXPORTS = [
     ("rtg_svgf_moments", C.c_int, [C.c_void_p, f32p]),
     ("rtg_svgf_copy_device", C.c_int, [C.c_void_p, C.c_void_p]),
     ("rtg_svgf_ms", C.c_int, [C.c_void_p] + [C.POINTER(C.c_double)] * 4),
+    # the fused first-hit pass (rtg_gbuffer.hip)
+    ("rtg_gbuffer", C.c_int, [C.c_void_p, f32p, f32p, f32p, f32p]),
+    ("rtg_gbuffer_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
 ]
 
 RTH_EXPORTS = [

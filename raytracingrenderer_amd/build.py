@@ -32,7 +32,7 @@ DEVICE_SRC = ["device/rtg_trace.hip", "device/rtg_scene.hip", "device/rtg_render
               "device/rtg_shade.hip", "device/rtg_light.hip", "device/rtg_multi.hip", "device/rtg_bvh.hip",
               "device/rtg_denoise.hip", "device/rtg_env.hip", "device/rtg_light_pick.hip",
               "device/rtg_shade_phys.hip", "device/rtg_shade_mis.hip", "device/rtg_shade_trans.hip",
-              "device/rtg_temporal.hip", "device/rtg_svgf.hip"]
+              "device/rtg_temporal.hip", "device/rtg_svgf.hip", "device/rtg_gbuffer.hip"]
 # per-unit compile flags: k_shade's translation unit takes LLVM's max-ilp scheduler, which its
 # latency-bound body prefers, while the traversal keeps the default; the traversal's
 # unit is built without SLP vectorisation, whose packed FP32 pairs in the triangle test held k_trace at
@@ -41,6 +41,8 @@ DEVICE_SRC = ["device/rtg_trace.hip", "device/rtg_scene.hip", "device/rtg_render
 # traversal's keep its flag: their kernels and rtg_scene.hip's host arithmetic were compiled with it.
 DEVICE_FLAGS = {"device/rtg_shade.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-fno-slp-vectorize"]}
 DEVICE_FLAGS.update({"device/rtg_%s.hip" % u: ["-fno-slp-vectorize"] for u in ("trace", "scene", "render", "api")})
+# k_gbuffer (the fused first-hit pass) shares the shading helpers of rtg_dev.h with those units
+DEVICE_FLAGS["device/rtg_gbuffer.hip"] = ["-fno-slp-vectorize"]
 # k_shade_pick (rtg_set_light_sampling) is k_shade's body: its unit takes k_shade's flags
 DEVICE_FLAGS["device/rtg_light_pick.hip"] = DEVICE_FLAGS["device/rtg_shade.hip"]
 # ... and so is k_shade_phys (rtg_set_material_model)

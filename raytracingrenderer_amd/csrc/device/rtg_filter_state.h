@@ -1,6 +1,7 @@
 // rtg_filter_state.h — host-only declarations shared by the film-filter units: the denoiser
 // (rtg_denoise.hip), the temporal unit (rtg_temporal.hip) and the variance-guided chain that joins them
-// (rtg_svgf.hip). No kernel and no device function lives here: each unit keeps its own.
+// (rtg_svgf.hip), and the fused first-hit pass that feeds them (rtg_gbuffer.hip). No kernel and no device
+// function lives here: each unit keeps its own.
 #pragma once
 #include "rtg_internal.h"
 
@@ -24,6 +25,7 @@ struct TemporalState {
     rtg_camera_proj hproj{}, cproj{};
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     double guide_ms = 0.0, accumulate_ms = 0.0;
+    double gbuffer_ms = 0.0;                // the fused pass of the last rtg_gbuffer / rtg_svgf_accumulate (0: none ran)
     SvgfState* sv = nullptr;                // allocated by the first rtg_svgf_accumulate
 };
 
@@ -36,7 +38,6 @@ struct SvgfState {
     float* var = nullptr;                   // the variance fed to level 0
     float4* xpos = nullptr;                 // the current guide's {X, t} halves, packed for the filter's taps
     float* out = nullptr;                   // last result, tightly packed rgb
-    unsigned long long* stats_keep = nullptr;  // the device counters, held while the guides render
     hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     double guide_ms = 0.0, accumulate_ms = 0.0, variance_ms = 0.0, filter_ms = 0.0;
 };
@@ -61,6 +62,8 @@ int temporal_check(const char* who, const rtg_temporal_params* p);
 bool same_camera(const DevCamera& a, const rtg_camera_proj& ap, const DevCamera& b, const rtg_camera_proj& bp);
 // the guide of the handle's camera, queued on h's stream (see its definition)
 int current_guide(rtg_handle* h, const float4** guide, bool* traced);
+// ... and the denoiser's guides with it, by one fused first-hit pass when either is missing (see its definition)
+int current_gbuffer(rtg_handle* h, const float4** guide, bool* traced);
 // after an accumulate whose result is complete: hist flips, and unless the camera was the history's, the
 // stored camera and guide (g, as current_guide gave it) become the current ones
 void temporal_advance(rtg_handle* h, bool unchanged, const float4* g);
@@ -69,5 +72,8 @@ void temporal_advance(rtg_handle* h, bool unchanged, const float4* g);
 int denoise_state(rtg_handle* h);
 // the albedo / shading-normal guides, rendered and packed when dropped; wait: the host waits for them
 int ensure_guides(rtg_handle* h, bool wait = true);
+// rtg_gbuffer.hip: k_gbuffer on st, from the first hits in pb into geo (2 records per pixel) and d's three
+// guide buffers
+int launch_gbuffer(rtg_handle* h, const PathBufs& pb, float4* geo, DenoiseState& d, hipStream_t st);
 // rtg_svgf.hip: frees t.sv (temporal_release)
 void svgf_release(TemporalState& t);

@@ -333,7 +333,7 @@ void svgf_release(TemporalState& t) {
     SvgfState* s = t.sv;
     if (!s) return;
     (void)hipFree(s->mom[0]); (void)hipFree(s->mom[1]); (void)hipFree(s->col[0]); (void)hipFree(s->col[1]);
-    (void)hipFree(s->var); (void)hipFree(s->out); (void)hipFree(s->stats_keep); (void)hipFree(s->xpos);
+    (void)hipFree(s->var); (void)hipFree(s->out); (void)hipFree(s->xpos);
     for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
     delete s;
     t.sv = nullptr;
@@ -352,7 +352,6 @@ static int ensure_state(TemporalState& t) {
     HIPOK(hipMalloc((void**)&s.var, t.n * sizeof(float)));
     HIPOK(hipMalloc((void**)&s.xpos, t.n * sizeof(float4)));
     HIPOK(hipMalloc((void**)&s.out, 3 * t.n * sizeof(float)));
-    HIPOK(hipMalloc((void**)&s.stats_keep, RTG_NSTATS * sizeof(unsigned long long)));
     return RTG_OK;
 }
 
@@ -411,15 +410,10 @@ int rtg_svgf_accumulate(rtg_handle* h, const rtg_svgf_params* p, float* out) {
     const float4* g = nullptr;  // the current geometry guide: the history's own when the camera is its camera
     bool traced = false;
     HIPOK(hipEventRecord(s.ev[0], st));
-    if (int rc = current_guide(h, &g, &traced)) return rc;
+    // one fused first-hit pass for the geometry guide and the denoiser's guides (nothing when both are at hand);
+    // it renders nothing, so the statistics have nothing to be put back
+    if (int rc = current_gbuffer(h, &g, &traced)) return rc;
     HIPOK(hipEventRecord(s.ev[1], st));
-    // The guides' two renders tally their camera rays into the device counters behind rtg_stats (k_tally), as
-    // they do under rtg_denoise; this call leaves the statistics as they were, so the counters are put back.
-    const bool render_guides = !h->dn->guides_ready;
-    const size_t stats_bytes = RTG_NSTATS * sizeof(unsigned long long);
-    if (render_guides) HIPOK(hipMemcpyAsync(s.stats_keep, h->d_stats, stats_bytes, hipMemcpyDeviceToDevice, st));
-    if (int rc = ensure_guides(h, false)) return rc;
-    if (render_guides) HIPOK(hipMemcpyAsync(h->d_stats, s.stats_keep, stats_bytes, hipMemcpyDeviceToDevice, st));
 
     SvgfTemporalArgs a{};
     a.film = h->d_film;
@@ -493,6 +487,7 @@ int rtg_svgf_accumulate(rtg_handle* h, const rtg_svgf_params* p, float* out) {
     HIPOK(hipStreamSynchronize(st));
     float ms = 0.0f;
     s.guide_ms = (traced && hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) == hipSuccess) ? ms : 0.0;
+    t.gbuffer_ms = s.guide_ms;
     if (hipEventElapsedTime(&ms, s.ev[2], s.ev[3]) == hipSuccess) s.accumulate_ms = ms;
     if (hipEventElapsedTime(&ms, s.ev[3], s.ev[4]) == hipSuccess) s.variance_ms = ms;
     if (hipEventElapsedTime(&ms, s.ev[4], s.ev[5]) == hipSuccess) s.filter_ms = ms;

@@ -197,18 +197,12 @@ bool same_camera(const DevCamera& a, const rtg_camera_proj& ap, const DevCamera&
     return std::memcmp(&a, &b, sizeof(DevCamera)) == 0 && std::memcmp(&ap, &bp, sizeof(rtg_camera_proj)) == 0;
 }
 
-// The guide of the handle's camera, on h's stream (no host wait): the history's own when the camera is
-// its camera, the cache's when it holds this camera, else traced into the cache. One pinhole ray through
-// every pixel centre, whatever rtg_set_camera_sampling says, by the generate and traversal kernels (the
-// camera pass of rtg_render_instant_radiosity), then k_geometry_guide. The caller has joined the queued
-// frames and waited for the stream (slot 0's buffers are free). The options, the statistics and the film
-// are not touched: no counting kernels, no tally, no film write.
-int current_guide(rtg_handle* h, const float4** guide, bool* traced) {
-    TemporalState& t = *h->tp;
-    *traced = false;
-    if (t.have_hist && same_camera(h->cam, h->proj, t.hcam, t.hproj)) { *guide = t.hguide; return RTG_OK; }
-    if (t.cache_ready && same_camera(h->cam, h->proj, t.ccam, t.cproj)) { *guide = t.cguide; return RTG_OK; }
-    t.cache_ready = false;
+// The first hits of the handle's camera into slot 0's buffers, on h's stream (no host wait): one pinhole ray
+// through every pixel centre, whatever rtg_set_camera_sampling says, by the generate and traversal kernels
+// (the camera pass of rtg_render_instant_radiosity). The caller has joined the queued frames and waited for
+// the stream (slot 0's buffers are free). The options, the statistics and the film are not touched: no
+// counting kernels, no tally, no film write.
+static int trace_first_hits(rtg_handle* h, PathBufs** out) {
     hipStream_t st = h->stream;
     int rc;
     if ((rc = set_pixels(h, nullptr, 0))) return rc;
@@ -227,6 +221,7 @@ int current_guide(rtg_handle* h, const float4** guide, bool* traced) {
     ca.mode = RTG_INTEGRATOR_PATH;
     ca.cam = h->cam;
     HIPOK(hipMemsetAsync(pb.ctr, 0, 2 * sizeof(Counters), st));
+    (void)hipGetLastError();  // drop any stale error left by other code on this thread (as render_impl does)
     if ((rc = launch_generate(h, ca, pb, st))) return rc;
     TraceIO io{};
     io.stats = h->d_stats;
@@ -244,14 +239,57 @@ int current_guide(rtg_handle* h, const float4** guide, bool* traced) {
     rc = launch_trace(h, io, st);
     h->count = keep_count;
     if (rc) return rc;
-    hipLaunchKernelGGL(k_geometry_guide, dim3((npix + 255) / 256), dim3(256), 0, st, h->sv.tris48,
-                       (const unsigned*)h->d_pix, npix, (const float4*)pb.hits, (const float4*)pb.ray_d, h->cam.ox,
+    *out = &pb;
+    return RTG_OK;
+}
+
+// The guide of the handle's camera, on h's stream (no host wait): the history's own when the camera is
+// its camera, the cache's when it holds this camera, else traced into the cache (trace_first_hits, then
+// k_geometry_guide).
+int current_guide(rtg_handle* h, const float4** guide, bool* traced) {
+    TemporalState& t = *h->tp;
+    *traced = false;
+    if (t.have_hist && same_camera(h->cam, h->proj, t.hcam, t.hproj)) { *guide = t.hguide; return RTG_OK; }
+    if (t.cache_ready && same_camera(h->cam, h->proj, t.ccam, t.cproj)) { *guide = t.cguide; return RTG_OK; }
+    t.cache_ready = false;
+    PathBufs* pb = nullptr;
+    if (int rc = trace_first_hits(h, &pb)) return rc;
+    hipLaunchKernelGGL(k_geometry_guide, dim3((h->npix + 255) / 256), dim3(256), 0, h->stream, h->sv.tris48,
+                       (const unsigned*)h->d_pix, h->npix, (const float4*)pb->hits, (const float4*)pb->ray_d, h->cam.ox,
                        h->cam.oy, h->cam.oz, t.cguide);
     LAUNCH_OK("k_geometry_guide");
     t.ccam = h->cam;
     t.cproj = h->proj;
     t.cache_ready = true;
     *guide = t.cguide;
+    *traced = true;
+    return RTG_OK;
+}
+
+// The guide of the handle's camera as current_guide gives it, and the denoiser's albedo / shading-normal guides
+// with it (rtg_gbuffer.hip). Nothing runs when the geometry guide is at hand (the history's own
+// or the cache's) and the denoiser's guides are ready. Otherwise one pass on h's stream (no host wait):
+// trace_first_hits, then k_gbuffer into the guide cache and the denoiser's three guide buffers, and both caches
+// are valid for this camera. The camera rays are traced once; the film, Film::SPP, the integrator, the options,
+// the statistics, launch_ms / launch_rays and the camera-sampling record are not touched. The caller has joined
+// the queued frames, waited for the stream, and allocated both states (temporal_state, denoise_state).
+int current_gbuffer(rtg_handle* h, const float4** guide, bool* traced) {
+    TemporalState& t = *h->tp;
+    DenoiseState& d = *h->dn;
+    *traced = false;
+    const bool own = t.have_hist && same_camera(h->cam, h->proj, t.hcam, t.hproj);
+    const bool cached = t.cache_ready && same_camera(h->cam, h->proj, t.ccam, t.cproj);
+    if ((own || cached) && d.guides_ready) { *guide = own ? t.hguide : t.cguide; return RTG_OK; }
+    t.cache_ready = false;
+    d.guides_ready = false;
+    PathBufs* pb = nullptr;
+    if (int rc = trace_first_hits(h, &pb)) return rc;
+    if (int rc = launch_gbuffer(h, *pb, t.cguide, d, h->stream)) return rc;
+    t.ccam = h->cam;
+    t.cproj = h->proj;
+    t.cache_ready = true;
+    d.guides_ready = true;
+    *guide = own ? t.hguide : t.cguide;  // (the same bits; the history keeps its own buffer)
     *traced = true;
     return RTG_OK;
 }

@@ -43,6 +43,10 @@
 // Camera pose (rtg_set_camera): -from "x y z" -to "x y z" -up "x y z" -fov degrees override scene.json's
 // pose through rth_camera_look_at, the loader's own camera code; each is optional and keeps the scene's
 // value when absent. For one device and for -gpus / -devices alike.
+// AOVs (rtg_gbuffer): -aov PREFIX writes, after the render, PREFIX_albedo.hdr, PREFIX_normal.hdr (the
+// denoiser's guides: first-hit albedo and |shading normal|) and PREFIX_depth.hdr (the first hit's distance t in
+// all three channels, 0 on a miss) as RGBE, from one traversal of the pixel-centre camera rays; with -from / -to
+// / -up / -fov they are the AOVs of that pose. One device only.
 // Multi-GPU (one node): -gpus N renders on devices 0..N-1, -devices a,b,... on a list. Rank r
 // renders the 32x32 tiles with (tile_x + tile_y) % N == r, and the film is assembled on the first
 // device from every device's own tiles (packed, one RCCL send per device, scattered) before it is
@@ -57,6 +61,7 @@
 #include <cstdlib>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 static int die(const char* what, const char* msg) {
@@ -163,6 +168,8 @@ int main(int argc, char** argv) {
         if (rth_camera_look_at(from, to, up, fov, info.width, info.height, flip_x, &new_cam, &new_proj) != 0)
             return die("rth_camera_look_at", rth_last_error());
     }
+    const std::string aov = get("-aov", "");
+    if (!aov.empty() && !devices.empty()) return die("-aov", "one device only (not with -gpus / -devices)");
     rtg_handle* rt = nullptr;
     rtg_group* grp = nullptr;
     if (devices.empty()) {
@@ -255,6 +262,23 @@ int main(int argc, char** argv) {
         if (rth_save_hdr(den_name.c_str(), info.width, info.height, den.data(), 1) != 0)  // already a mean
             return die("saveHDR", rth_last_error());
         std::printf("wrote %s\n", den_name.c_str());
+    }
+    if (!aov.empty()) {
+        const size_t n = (size_t)info.width * info.height;
+        std::vector<float> pos_t(n * 4), alb(n * 3), nrm(n * 3), depth(n * 3);
+        if (rtg_gbuffer(rt, pos_t.data(), nullptr, alb.data(), nrm.data()) != 0) return die("rtg_gbuffer", rtg_last_error());
+        for (size_t i = 0; i < n; ++i) {
+            const float t = pos_t[4 * i + 3];
+            depth[3 * i] = depth[3 * i + 1] = depth[3 * i + 2] = t < 3.40282347e+38f ? t : 0.0f;
+        }
+        const std::pair<const char*, const float*> outs[3] = {{"_albedo.hdr", alb.data()}, {"_normal.hdr", nrm.data()},
+                                                              {"_depth.hdr", depth.data()}};
+        for (const auto& o : outs) {
+            const std::string name = aov + o.first;
+            if (rth_save_hdr(name.c_str(), info.width, info.height, o.second, 1) != 0)  // values, not sums
+                return die("saveHDR", rth_last_error());
+            std::printf("wrote %s\n", name.c_str());
+        }
     }
     if (rt) rtg_destroy(rt);
     if (grp) rtg_group_destroy(grp);

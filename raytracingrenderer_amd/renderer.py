@@ -571,6 +571,27 @@ class RayTracer:
         _check(self._lib.rtg_svgf_ms(self._h, *[C.byref(x) for x in v]), self._lib.rtg_last_error)
         return tuple(x.value for x in v)
 
+    def gbuffer(self):
+        """The first-hit AOVs of the current camera from one traversal of its pixel-centre rays (rtg_gbuffer):
+        "pos_t" and "normal_id", (H, W, 4) float32, are geometry_guide()'s two images; "albedo" and "normal",
+        (H, W, 3) float32, are guides()'s. Depth is pos_t[..., 3] (FLT_MAX on a miss), the triangle id
+        normal_id[..., 3].view(np.int32) (-1 on a miss). The call fills the caches those calls, temporal(),
+        svgf() and denoise() read, so none of them traces a camera ray afterwards until set_camera(). The film,
+        SPP and the settings stay as they were. Waits for queued frames first."""
+        shape = (self.height, self.width)
+        out = {"pos_t": np.zeros(shape + (4,), np.float32), "normal_id": np.zeros(shape + (4,), np.float32),
+               "albedo": np.zeros(shape + (3,), np.float32), "normal": np.zeros(shape + (3,), np.float32)}
+        ptrs = [N.ptr(out[k], C.c_float) for k in ("pos_t", "normal_id", "albedo", "normal")]
+        _check(self._lib.rtg_gbuffer(self._h, *ptrs), self._lib.rtg_last_error)
+        return out
+
+    def gbuffer_ms(self):
+        """Device time of the fused first-hit pass in the last gbuffer() or svgf(), in ms (0 when the caches
+        served it)."""
+        v = C.c_double()
+        _check(self._lib.rtg_gbuffer_ms(self._h, C.byref(v)), self._lib.rtg_last_error)
+        return v.value
+
     def set_camera_sampling(self, filter="none", filter_radius=None, lens_radius=0.0, focal_distance=1.0):
         """Anti-aliasing and depth of field (rtg_set_camera_sampling). filter "none" (default: every
         sample through the pixel centre, as renderTile), "box" or "tent": sample s of a pixel crosses

@@ -146,38 +146,20 @@ int denoise_check_params(const char* who, const rtg_denoise_params* p) {
     return RTG_OK;
 }
 
-static int check_size(const char* who, uint32_t w, uint32_t h) {
-    if (w == 0 || h == 0 || w > 65535u || h > 65535u || (uint64_t)w * h > (1ull << 28)) {
-        g_err = std::string(who) + ": image size must be 1..65535 per side and at most 2^28 pixels";
-        return RTG_ERR_ARG;
-    }
-    return RTG_OK;
-}
-
-static void free_bufs(DenoiseState& d) {
-    (void)hipFree(d.col[0]); (void)hipFree(d.col[1]); (void)hipFree(d.guide);
-    (void)hipFree(d.albedo); (void)hipFree(d.normal); (void)hipFree(d.out);
-    d.col[0] = d.col[1] = d.guide = nullptr;
-    d.albedo = d.normal = d.out = nullptr;
-    d.n = 0;
-}
-
+// d's six buffers for n pixels
 static int alloc_bufs(DenoiseState& d, size_t n) {
-    if (d.n == n) return RTG_OK;
-    free_bufs(d);
-    HIPOK(hipMalloc((void**)&d.col[0], n * sizeof(float4)));
-    HIPOK(hipMalloc((void**)&d.col[1], n * sizeof(float4)));
-    HIPOK(hipMalloc((void**)&d.guide, 2 * n * sizeof(float4)));
-    HIPOK(hipMalloc((void**)&d.albedo, 3 * n * sizeof(float)));
-    HIPOK(hipMalloc((void**)&d.normal, 3 * n * sizeof(float)));
-    HIPOK(hipMalloc((void**)&d.out, 3 * n * sizeof(float)));
+    for (DevBuf<float4>& b : d.col)
+        if (int rc = b.alloc(n)) return rc;
+    if (int rc = d.guide.alloc(2 * n)) return rc;
+    for (DevBuf<float>* b : {&d.albedo, &d.normal, &d.out})
+        if (int rc = b->alloc(3 * n)) return rc;
     d.n = n;
     return RTG_OK;
 }
 
 static int pack_guides(DenoiseState& d, hipStream_t st) {
-    hipLaunchKernelGGL(k_dn_pack_guide, dim3((unsigned)((d.n + 255) / 256)), dim3(256), 0, st, (const float*)d.albedo,
-                       (const float*)d.normal, d.n, d.guide);
+    hipLaunchKernelGGL(k_dn_pack_guide, dim3((unsigned)((d.n + 255) / 256)), dim3(256), 0, st, (const float*)d.albedo.p,
+                       (const float*)d.normal.p, d.n, d.guide.p);
     LAUNCH_OK("k_dn_pack_guide");
     return RTG_OK;
 }
@@ -187,10 +169,10 @@ static int filter(DenoiseState& d, hipStream_t st, uint32_t W, uint32_t H, const
                   const rtg_denoise_params& p) {
     const size_t n = (size_t)W * H;
     const dim3 lin((unsigned)((n + 255) / 256));
-    hipLaunchKernelGGL(k_dn_pack_colour, lin, dim3(256), 0, st, d_sum, (float)spp, n, d.col[0]);
+    hipLaunchKernelGGL(k_dn_pack_colour, lin, dim3(256), 0, st, d_sum, (float)spp, n, d.col[0].p);
     LAUNCH_OK("k_dn_pack_colour");
     DenoiseArgs a{};
-    a.guide = d.guide;
+    a.guide = d.guide.p;
     a.W = (int)W;
     a.H = (int)H;
     a.m = (int)p.normal_squarings;
@@ -198,26 +180,21 @@ static int filter(DenoiseState& d, hipStream_t st, uint32_t W, uint32_t H, const
     a.alb_on = p.sigma_albedo > 0.0f;
     a.ia = a.alb_on ? 1.0f / (p.sigma_albedo * p.sigma_albedo) : 0.0f;
     for (uint32_t i = 0; i < p.iterations; ++i) {
-        a.cin = d.col[i & 1];
-        a.cout = d.col[(i + 1) & 1];
+        a.cin = d.col[i & 1].p;
+        a.cout = d.col[(i + 1) & 1].p;
         a.step = 1 << i;
         const float sc = ldexpf(p.sigma_colour, -(int)i);
         a.ic = a.col_on ? 1.0f / (sc * sc) : 0.0f;
         hipLaunchKernelGGL(k_dn_atrous, dim3((W + 63) / 64, (H + 3) / 4), dim3(256), 0, st, a);
         LAUNCH_OK("k_dn_atrous");
     }
-    hipLaunchKernelGGL(k_dn_unpack, lin, dim3(256), 0, st, (const float4*)d.col[p.iterations & 1], n, d.out);
+    hipLaunchKernelGGL(k_dn_unpack, lin, dim3(256), 0, st, (const float4*)d.col[p.iterations & 1].p, n, d.out.p);
     LAUNCH_OK("k_dn_unpack");
     return RTG_OK;
 }
 
 void denoise_release(rtg_handle* h) {
-    DenoiseState* d = h->dn;
-    if (!d) return;
-    free_bufs(*d);
-    if (d->e0) (void)hipEventDestroy(d->e0);
-    if (d->e1) (void)hipEventDestroy(d->e1);
-    delete d;
+    delete h->dn;  // (its buffers and its events with it)
     h->dn = nullptr;
 }
 
@@ -225,17 +202,16 @@ void denoise_drop_guides(rtg_handle* h) {
     if (h->dn) h->dn->guides_ready = false;
 }
 
-// the handle's denoiser state, allocated on first use
-static int ensure_state(rtg_handle* h) {
-    if (!h->dn) {
-        h->dn = new DenoiseState();
-        HIPOK(hipEventCreate(&h->dn->e0));
-        HIPOK(hipEventCreate(&h->dn->e1));
-    }
-    return alloc_bufs(*h->dn, (size_t)h->W * h->H);
+// The handle's denoiser state, built on first use (the film's size never changes): a local one, handed to the
+// handle by the last statement, so a failed allocation leaves the handle without one and the next call builds again.
+int denoise_state(rtg_handle* h) {
+    if (h->dn) return RTG_OK;
+    auto d = std::make_unique<DenoiseState>();
+    if (int rc = d->ev.create()) return rc;
+    if (int rc = alloc_bufs(*d, (size_t)h->W * h->H)) return rc;
+    h->dn = d.release();
+    return RTG_OK;
 }
-
-int denoise_state(rtg_handle* h) { return ensure_state(h); }
 
 // The guides, once per handle: 1 sample of the albedo and of the shading-normal integrator into
 // scratch films (the film swap of rtg_render_adaptive), every tile, then packed. Both estimators
@@ -256,7 +232,7 @@ int ensure_guides(rtg_handle* h, bool wait) {
     h->count = h->timing = 0;
     int rc = RTG_OK;
     const int modes[2] = {RTG_INTEGRATOR_ALBEDO, RTG_INTEGRATOR_NORMALS};
-    float* const films[2] = {d.albedo, d.normal};
+    float* const films[2] = {d.albedo.p, d.normal.p};
     for (int k = 0; k < 2 && rc == RTG_OK; ++k) {
         if (hipMemsetAsync(films[k], 0, nf, h->stream) != hipSuccess) {
             g_err = "rtg_denoise: clearing a guide film failed";
@@ -285,16 +261,16 @@ int ensure_guides(rtg_handle* h, bool wait) {
 // Filters d_sum / spp (a film on h's device, ready on h's stream or earlier) with h's guides into
 // h's result buffer; waits for it, and copies it to `out` when given.
 int denoise_film(rtg_handle* h, const float* d_sum, uint32_t spp, const rtg_denoise_params* p, float* out) {
-    if (int rc = ensure_state(h)) return rc;
+    if (int rc = denoise_state(h)) return rc;
     if (int rc = ensure_guides(h)) return rc;
     DenoiseState& d = *h->dn;
-    HIPOK(hipEventRecord(d.e0, h->stream));
+    HIPOK(hipEventRecord(d.ev[0], h->stream));
     if (int rc = filter(d, h->stream, (uint32_t)h->W, (uint32_t)h->H, d_sum, spp, *p)) return rc;
-    HIPOK(hipEventRecord(d.e1, h->stream));
-    if (out) HIPOK(hipMemcpyAsync(out, d.out, d.n * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPOK(hipEventRecord(d.ev[1], h->stream));
+    if (out) HIPOK(hipMemcpyAsync(out, d.out.p, d.n * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPOK(hipStreamSynchronize(h->stream));
     float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, d.e0, d.e1) == hipSuccess) d.ms = ms;
+    if (hipEventElapsedTime(&ms, d.ev[0], d.ev[1]) == hipSuccess) d.ms = ms;
     d.have_result = true;
     return RTG_OK;
 }
@@ -313,35 +289,27 @@ int rtg_denoise_defaults(rtg_denoise_params* p) {
 int rtg_denoise_images(int device, uint32_t w, uint32_t h, const float* colour, const float* albedo,
                        const float* normal, const rtg_denoise_params* p, float* out) {
     if (!colour || !albedo || !normal || !out) { g_err = "rtg_denoise_images: null image"; return RTG_ERR_ARG; }
-    if (int rc = check_size("rtg_denoise_images", w, h)) return rc;
+    if (int rc = check_size("rtg_denoise_images", w, h, "image size")) return rc;
     if (int rc = denoise_check_params("rtg_denoise_images", p)) return rc;
     HIPOK(hipSetDevice(device));
-    DenoiseState d;
-    float* d_sum = nullptr;
-    const size_t nf = (size_t)w * h * 3 * sizeof(float);
-    auto run = [&]() -> int {
-        if (int rc = alloc_bufs(d, (size_t)w * h)) return rc;
-        HIPOK(hipMalloc((void**)&d_sum, nf));
-        HIPOK(hipMemcpy(d_sum, colour, nf, hipMemcpyHostToDevice));
-        HIPOK(hipMemcpy(d.albedo, albedo, nf, hipMemcpyHostToDevice));
-        HIPOK(hipMemcpy(d.normal, normal, nf, hipMemcpyHostToDevice));
-        if (int rc = pack_guides(d, nullptr)) return rc;
-        if (int rc = filter(d, nullptr, w, h, d_sum, 1u, *p)) return rc;  // x / 1.0f is x
-        HIPOK(hipStreamSynchronize(nullptr));
-        HIPOK(hipMemcpy(out, d.out, nf, hipMemcpyDeviceToHost));
-        return RTG_OK;
-    };
-    const int rc = run();
-    (void)hipFree(d_sum);
-    free_bufs(d);
-    return rc;
+    DenoiseState d;  // local: freed on every way out
+    DevBuf<float> d_sum;
+    const size_t n = (size_t)w * h;
+    if (int rc = alloc_bufs(d, n)) return rc;
+    if (int rc = d_sum.upload(colour, 3 * n)) return rc;
+    HIPOK(hipMemcpy(d.albedo.p, albedo, 3 * n * sizeof(float), hipMemcpyHostToDevice));
+    HIPOK(hipMemcpy(d.normal.p, normal, 3 * n * sizeof(float), hipMemcpyHostToDevice));
+    if (int rc = pack_guides(d, nullptr)) return rc;
+    if (int rc = filter(d, nullptr, w, h, d_sum.p, 1u, *p)) return rc;  // x / 1.0f is x
+    HIPOK(hipStreamSynchronize(nullptr));
+    return d.out.download(out, 3 * n);
 }
 
 int rtg_denoise(rtg_handle* h, const rtg_denoise_params* p, float* out) {
     if (!h) { g_err = "rtg_denoise: null handle"; return RTG_ERR_ARG; }
     if (int rc = denoise_check_params("rtg_denoise", p)) return rc;
     if (h->spp == 0) { g_err = "rtg_denoise: the film holds no samples (spp == 0)"; return RTG_ERR_ARG; }
-    if (int rc = check_size("rtg_denoise", (uint32_t)h->W, (uint32_t)h->H)) return rc;
+    if (int rc = check_size("rtg_denoise", h->W, h->H, "image size")) return rc;
     HIPOK(hipSetDevice(h->device));
     if (int rc = join_frames(h)) return rc;  // the film holds every queued frame first
     return denoise_film(h, h->d_film, h->spp, p, out);
@@ -349,24 +317,21 @@ int rtg_denoise(rtg_handle* h, const rtg_denoise_params* p, float* out) {
 
 int rtg_denoise_guides(rtg_handle* h, float* albedo, float* normal) {
     if (!h) { g_err = "rtg_denoise_guides: null handle"; return RTG_ERR_ARG; }
-    if (int rc = check_size("rtg_denoise_guides", (uint32_t)h->W, (uint32_t)h->H)) return rc;
+    if (int rc = check_size("rtg_denoise_guides", h->W, h->H, "image size")) return rc;
     HIPOK(hipSetDevice(h->device));
     if (int rc = join_frames(h)) return rc;
-    if (int rc = ensure_state(h)) return rc;
+    if (int rc = denoise_state(h)) return rc;
     if (int rc = ensure_guides(h)) return rc;
-    const size_t nf = h->dn->n * 3 * sizeof(float);
-    if (albedo) HIPOK(hipMemcpy(albedo, h->dn->albedo, nf, hipMemcpyDeviceToHost));
-    if (normal) HIPOK(hipMemcpy(normal, h->dn->normal, nf, hipMemcpyDeviceToHost));
+    if (albedo)
+        if (int rc = h->dn->albedo.download(albedo, 3 * h->dn->n)) return rc;
+    if (normal)
+        if (int rc = h->dn->normal.download(normal, 3 * h->dn->n)) return rc;
     return RTG_OK;
 }
 
 int rtg_denoise_copy_device(rtg_handle* h, void* dst_device) {
-    if (!h || !dst_device) { g_err = "rtg_denoise_copy_device: null argument"; return RTG_ERR_ARG; }
-    if (!h->dn || !h->dn->have_result) { g_err = "rtg_denoise_copy_device: no denoised result yet"; return RTG_ERR_ARG; }
-    HIPOK(hipSetDevice(h->device));
-    HIPOK(hipMemcpyAsync(dst_device, h->dn->out, h->dn->n * 3 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    HIPOK(hipStreamSynchronize(h->stream));
-    return RTG_OK;
+    const bool have = h && h->dn && h->dn->have_result;
+    return copy_result("rtg_denoise_copy_device", h, have ? h->dn->out.p : nullptr, dst_device, "no denoised result yet");
 }
 
 double rtg_denoise_ms(rtg_handle* h) { return (h && h->dn) ? h->dn->ms : 0.0; }

@@ -1,9 +1,15 @@
-// rtg_filter_state.h — host-only declarations shared by the film-filter units: the denoiser
-// (rtg_denoise.hip), the temporal unit (rtg_temporal.hip) and the variance-guided chain that joins them
-// (rtg_svgf.hip), and the fused first-hit pass that feeds them (rtg_gbuffer.hip). No kernel and no device
-// function lives here: each unit keeps its own.
+// rtg_filter_state.h — the host layer shared by the film-filter units: the denoiser (rtg_denoise.hip), the
+// temporal unit (rtg_temporal.hip), the variance-guided chain that joins them (rtg_svgf.hip) and the fused
+// first-hit pass that feeds them (rtg_gbuffer.hip). Their states own their device memory (DevBuf) and their
+// timing events (DevEvents), so releasing one is `delete`; each is built as a local object and handed to the
+// handle only once every allocation has succeeded, so the handle never holds a half-built
+// one. No kernel and no device function lives here: the two temporal kernels share rtg_reproject.h, every
+// other kernel is its unit's own.
 #pragma once
 #include "rtg_internal.h"
+
+#include <cstring>
+#include <memory>
 
 struct TemporalProj {  // the history camera's projectOntoCamera state
     float P[16];       // projectionMatrix
@@ -11,69 +17,103 @@ struct TemporalProj {  // the history camera's projectOntoCamera state
     float W, H;
 };
 
-struct SvgfState;  // rtg_svgf.hip's buffers, below
-
-struct TemporalState {
-    size_t n = 0;                           // pixels the buffers hold
-    float4* hist[2] = {nullptr, nullptr};   // hist[cur] is H
-    int cur = 0;
-    float4* hguide = nullptr;               // the history camera's guide (valid when have_hist)
-    float4* cguide = nullptr;               // the guide cache (valid for ccam / cproj when cache_ready)
-    float* out = nullptr;                   // last result, tightly packed rgb
-    bool have_hist = false, cache_ready = false, have_result = false;
-    DevCamera hcam{}, ccam{};
-    rtg_camera_proj hproj{}, cproj{};
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    double guide_ms = 0.0, accumulate_ms = 0.0;
-    double gbuffer_ms = 0.0;                // the fused pass of the last rtg_gbuffer / rtg_svgf_accumulate (0: none ran)
-    SvgfState* sv = nullptr;                // allocated by the first rtg_svgf_accumulate
-};
-
-struct SvgfState {
-    float2* mom[2] = {nullptr, nullptr};    // mom[cur] is M = {mu1, mu2}, the ping-pong partner of hist
+struct SvgfState {  // rtg_svgf.hip's part of the temporal state
+    DevBuf<float2> mom[2];                  // mom[cur] is M = {mu1, mu2}, the ping-pong partner of hist
     int cur = 0;
     bool mom_valid = false;                 // M belongs to H (cleared by rtg_temporal_accumulate)
     bool have_result = false;
-    float4* col[2] = {nullptr, nullptr};    // {rgb, v}, the filter's ping-pong
-    float* var = nullptr;                   // the variance fed to level 0
-    float4* xpos = nullptr;                 // the current guide's {X, t} halves, packed for the filter's taps
-    float* out = nullptr;                   // last result, tightly packed rgb
-    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    DevBuf<float4> col[2];                  // {rgb, v}, the filter's ping-pong
+    DevBuf<float> var;                      // the variance fed to level 0
+    DevBuf<float4> xpos;                    // the current guide's {X, t} halves, packed for the filter's taps
+    DevBuf<float> out;                      // last result, tightly packed rgb
+    DevEvents<8> ev;
     double guide_ms = 0.0, accumulate_ms = 0.0, variance_ms = 0.0, filter_ms = 0.0;
+};
+
+struct TemporalState {
+    size_t n = 0;                           // pixels the buffers hold
+    DevBuf<float4> hist[2];                 // hist[cur] is H
+    int cur = 0;
+    DevBuf<float4> hguide;                  // the history camera's guide (valid when have_hist)
+    DevBuf<float4> cguide;                  // the guide cache (valid for ccam / cproj when cache_ready)
+    DevBuf<float> out;                      // last result, tightly packed rgb
+    bool have_hist = false, cache_ready = false, have_result = false;
+    DevCamera hcam{}, ccam{};
+    rtg_camera_proj hproj{}, cproj{};
+    DevEvents<4> ev;
+    double guide_ms = 0.0, accumulate_ms = 0.0;
+    double gbuffer_ms = 0.0;                // the fused pass of the last rtg_gbuffer / rtg_svgf_accumulate (0: none ran)
+    std::unique_ptr<SvgfState> sv;          // built by the first rtg_svgf_accumulate
 };
 
 struct DenoiseState {
     size_t n = 0;                  // pixels the buffers hold
-    float4* col[2] = {nullptr, nullptr};
-    float4* guide = nullptr;       // packed guides (valid when guides_ready)
-    float* albedo = nullptr;       // the guide films as rendered (rtg_denoise_guides)
-    float* normal = nullptr;
-    float* out = nullptr;          // last result, tightly packed rgb
+    DevBuf<float4> col[2];
+    DevBuf<float4> guide;          // packed guides (valid when guides_ready)
+    DevBuf<float> albedo;          // the guide films as rendered (rtg_denoise_guides)
+    DevBuf<float> normal;
+    DevBuf<float> out;             // last result, tightly packed rgb
     bool guides_ready = false, have_result = false;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    DevEvents<2> ev;               // (none in rtg_denoise_images' local state)
     double ms = 0.0;
 };
 
+// device time from event a to event b of a stage that ran and has finished; 0 for one that did not run
+static inline double stage_ms(bool ran, hipEvent_t a, hipEvent_t b) {
+    float ms = 0.0f;
+    return (ran && hipEventElapsedTime(&ms, a, b) == hipSuccess) ? ms : 0.0;
+}
+
 // rtg_temporal.hip
-// the handle's temporal state, allocated on first use (RTG_ERR_ARG for a film outside 1..65535 per side)
+// RTG_ERR_ARG ("who: <what> must be ...") for a size outside 1..65535 per side or above 2^28 pixels
+int check_size(const char* who, int64_t W, int64_t H, const char* what = "the film");
+// the handle's temporal state, built on first use (RTG_ERR_ARG for a film check_size refuses)
 int temporal_state(const char* who, rtg_handle* h);
 // RTG_ERR_ARG (with "who: ..." as the message) for parameters outside include/rtg.h's ranges
 int temporal_check(const char* who, const rtg_temporal_params* p);
 bool same_camera(const DevCamera& a, const rtg_camera_proj& ap, const DevCamera& b, const rtg_camera_proj& bp);
-// the guide of the handle's camera, queued on h's stream (see its definition)
-int current_guide(rtg_handle* h, const float4** guide, bool* traced);
-// ... and the denoiser's guides with it, by one fused first-hit pass when either is missing (see its definition)
-int current_gbuffer(rtg_handle* h, const float4** guide, bool* traced);
+// the guide of the handle's camera, queued on h's stream; with_denoiser: the denoiser's guides with it, by one
+// fused first-hit pass when either is missing (see its definition)
+int current_guide(rtg_handle* h, bool with_denoiser, const float4** guide, bool* traced);
+// a guide's W * H records downloaded, their halves split into the caller's two images (either may be null)
+int download_guide(const rtg_handle* h, const float4* guide, float* pos_t, float* normal_id);
 // after an accumulate whose result is complete: hist flips, and unless the camera was the history's, the
 // stored camera and guide (g, as current_guide gave it) become the current ones
 void temporal_advance(rtg_handle* h, bool unchanged, const float4* g);
+// A unit's last result (W * H rgb on the device, null: none yet, refused as "who: <none>") copied to device
+// memory on h's stream, and waited for
+int copy_result(const char* who, rtg_handle* h, const float* result, void* dst_device, const char* none = "no result yet");
 // rtg_denoise.hip
-// the handle's denoiser state, allocated on first use
+// the handle's denoiser state, built on first use
 int denoise_state(rtg_handle* h);
 // the albedo / shading-normal guides, rendered and packed when dropped; wait: the host waits for them
 int ensure_guides(rtg_handle* h, bool wait = true);
 // rtg_gbuffer.hip: k_gbuffer on st, from the first hits in pb into geo (2 records per pixel) and d's three
 // guide buffers
 int launch_gbuffer(rtg_handle* h, const PathBufs& pb, float4* geo, DenoiseState& d, hipStream_t st);
-// rtg_svgf.hip: frees t.sv (temporal_release)
-void svgf_release(TemporalState& t);
+
+// One temporal step's set-up, for TemporalArgs and SvgfTemporalArgs alike: whether the camera is the history's
+// (returned), the mode that follows, and every field the two kernels share but gcur, which the caller sets in
+// mode 2 once it has the current guide.
+template <class Args>
+static inline bool temporal_setup(const rtg_handle* h, const TemporalState& t, const rtg_temporal_params& p, Args& a) {
+    const bool unchanged = t.have_hist && same_camera(h->cam, h->proj, t.hcam, t.hproj);
+    a.film = h->d_film;
+    a.m = (float)h->spp;
+    a.mode = !t.have_hist ? 0 : (unchanged ? 1 : 2);
+    a.hin = t.hist[t.cur].p;
+    a.hout = t.hist[t.cur ^ 1].p;
+    a.W = h->W;
+    a.H = h->H;
+    a.max_history = p.max_history;
+    a.plane_tolerance = p.plane_tolerance;
+    a.normal_cos = p.normal_cos;
+    if (a.mode == 2) {
+        a.ghist = t.hguide.p;
+        std::memcpy(a.cam.P, t.hproj.proj, sizeof(a.cam.P));
+        std::memcpy(a.cam.C2V, t.hproj.camera_to_view, sizeof(a.cam.C2V));
+        a.cam.W = t.hcam.width;
+        a.cam.H = t.hcam.height;
+    }
+    return unchanged;
+}

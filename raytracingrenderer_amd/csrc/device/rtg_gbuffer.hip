@@ -16,8 +16,6 @@
 // list; no LDS, no atomics.
 #include "rtg_filter_state.h"
 
-#include <cstring>
-
 __global__ __launch_bounds__(256) void k_gbuffer(SceneView s, const unsigned* __restrict__ pixlist, unsigned npix,
                                                  const float4* __restrict__ hits, const float4* __restrict__ ray_d,
                                                  float ox, float oy, float oz, float4* __restrict__ geo,
@@ -89,8 +87,8 @@ __global__ __launch_bounds__(256) void k_gbuffer(SceneView s, const unsigned* __
 int launch_gbuffer(rtg_handle* h, const PathBufs& pb, float4* geo, DenoiseState& d, hipStream_t st) {
     const unsigned npix = h->npix;
     hipLaunchKernelGGL(k_gbuffer, dim3((npix + 255) / 256), dim3(256), 0, st, h->sv, (const unsigned*)h->d_pix, npix,
-                       (const float4*)pb.hits, (const float4*)pb.ray_d, h->cam.ox, h->cam.oy, h->cam.oz, geo, d.albedo,
-                       d.normal, d.guide);
+                       (const float4*)pb.hits, (const float4*)pb.ray_d, h->cam.ox, h->cam.oy, h->cam.oz, geo, d.albedo.p,
+                       d.normal.p, d.guide.p);
     LAUNCH_OK("k_gbuffer");
     return RTG_OK;
 }
@@ -106,22 +104,15 @@ int rtg_gbuffer(rtg_handle* h, float* pos_t, float* normal_id, float* albedo, fl
     const float4* g = nullptr;
     bool traced = false;
     HIPOK(hipEventRecord(t.ev[0], h->stream));
-    if (int rc = current_gbuffer(h, &g, &traced)) return rc;
+    if (int rc = current_guide(h, true, &g, &traced)) return rc;
     HIPOK(hipEventRecord(t.ev[1], h->stream));
     HIPOK(hipStreamSynchronize(h->stream));
-    float ms = 0.0f;
-    t.gbuffer_ms = (traced && hipEventElapsedTime(&ms, t.ev[0], t.ev[1]) == hipSuccess) ? ms : 0.0;
-    if (pos_t || normal_id) {
-        std::vector<float4> rec(2 * t.n);  // the two halves of a record go to the caller's two images
-        HIPOK(hipMemcpy(rec.data(), g, rec.size() * sizeof(float4), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < t.n; ++i) {
-            if (pos_t) std::memcpy(pos_t + 4 * i, &rec[2 * i], sizeof(float4));
-            if (normal_id) std::memcpy(normal_id + 4 * i, &rec[2 * i + 1], sizeof(float4));
-        }
-    }
-    const size_t nf = h->dn->n * 3 * sizeof(float);
-    if (albedo) HIPOK(hipMemcpy(albedo, h->dn->albedo, nf, hipMemcpyDeviceToHost));
-    if (shading_normal) HIPOK(hipMemcpy(shading_normal, h->dn->normal, nf, hipMemcpyDeviceToHost));
+    t.gbuffer_ms = stage_ms(traced, t.ev[0], t.ev[1]);
+    if (int rc = download_guide(h, g, pos_t, normal_id)) return rc;
+    if (albedo)
+        if (int rc = h->dn->albedo.download(albedo, 3 * t.n)) return rc;
+    if (shading_normal)
+        if (int rc = h->dn->normal.download(shading_normal, 3 * t.n)) return rc;
     return RTG_OK;
 }
 

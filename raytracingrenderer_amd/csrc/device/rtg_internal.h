@@ -323,6 +323,32 @@ struct DevBuf {
     }
 };
 
+// N timing events and their one owner: move-only, destroyed by the destructor (on the device that is
+// current then, as DevBuf). create makes all N or leaves none.
+template <int N>
+struct DevEvents {
+    hipEvent_t e[N] = {};
+    DevEvents() = default;
+    DevEvents(DevEvents&& o) noexcept { std::swap(e, o.e); }
+    DevEvents& operator=(DevEvents&& o) noexcept { std::swap(e, o.e); return *this; }
+    DevEvents(const DevEvents&) = delete;
+    DevEvents& operator=(const DevEvents&) = delete;
+    ~DevEvents() { reset(); }
+    void reset() {
+        for (hipEvent_t& x : e) {
+            if (x) (void)hipEventDestroy(x);
+            x = nullptr;
+        }
+    }
+    int create() {
+        reset();
+        const int rc = [this]() -> int { for (hipEvent_t& x : e) HIPOK(hipEventCreate(&x)); return RTG_OK; }();
+        if (rc) reset();
+        return rc;
+    }
+    hipEvent_t operator[](int i) const { return e[i]; }
+};
+
 // One device-code probe of the test suite on the null stream: `in` is uploaded, `out` allocated, and
 // launch(d) queues the kernel with d[k] the device copy of the k-th listed buffer (inputs, then
 // outputs); the outputs are copied back once it has run (a null dst: not wanted).

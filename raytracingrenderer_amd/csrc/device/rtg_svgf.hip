@@ -19,7 +19,7 @@
 // k_dn_atrous lays them out: every tap of a wave is a contiguous row segment at any step and the row tests
 // are wave-uniform. Direct reads (k_dn_atrous's LDS-staged variant measured slower). No
 // atomics; no address depends on a colour.
-#include "rtg_filter_state.h"
+#include "rtg_reproject.h"
 
 #include <cmath>
 #include <cstring>
@@ -62,33 +62,8 @@ struct SvgfFilterArgs {
     float plane_tolerance;
 };
 
-static __device__ __forceinline__ float sv_dot(float ax, float ay, float az, float bx, float by, float bz) {
-    return (ax * bx + ay * by) + az * bz;
-}
-
 static __device__ __forceinline__ float sv_lum(float r, float g, float b) {
     return (0.2126f * r + 0.7152f * g) + 0.0722f * b;
-}
-
-// Camera::projectOntoCamera in tp_project's operation order (rtg_temporal.hip)
-static __device__ __forceinline__ bool sv_project(const TemporalProj& c, float px, float py, float pz, float& x,
-                                                  float& y) {
-    const float* m = c.C2V;
-    const float vx = ((px * m[0] + py * m[1]) + pz * m[2]) + m[3];
-    const float vy = ((px * m[4] + py * m[5]) + pz * m[6]) + m[7];
-    const float vz = ((px * m[8] + py * m[9]) + pz * m[10]) + m[11];
-    const float* q = c.P;
-    const float v1x = ((vx * q[0] + vy * q[1]) + vz * q[2]) + q[3];
-    const float v1y = ((vx * q[4] + vy * q[5]) + vz * q[6]) + q[7];
-    float w = (((q[12] * vx) + (q[13] * vy)) + (q[14] * vz)) + q[15];
-    w = 1.0f / w;
-    x = ((v1x * w) + 1.0f) * 0.5f;
-    y = ((v1y * w) + 1.0f) * 0.5f;
-    if (x < 0 || x > 1.0f || y < 0 || y > 1.0f) return false;
-    x = x * c.W;
-    y = 1.0f - y;
-    y = y * c.H;
-    return true;
 }
 
 // k_temporal's definition for rgb and len, with the two moments carried over the same admitted taps
@@ -110,7 +85,7 @@ __global__ __launch_bounds__(256) void k_svgf_temporal(SvgfTemporalArgs a) {
     } else if (a.mode == 2) {
         const float4 g0 = a.gcur[2 * p], g1 = a.gcur[2 * p + 1];
         float fx, fy;
-        if (__float_as_int(g1.w) >= 0 && sv_project(a.cam, g0.x, g0.y, g0.z, fx, fy)) {
+        if (__float_as_int(g1.w) >= 0 && rp_project(a.cam, g0.x, g0.y, g0.z, fx, fy)) {
             const float u = fx - 0.5f, v = fy - 0.5f;
             const float x0 = floorf(u), y0 = floorf(v);
             const float ax = u - x0, ay = v - y0;
@@ -131,9 +106,9 @@ __global__ __launch_bounds__(256) void k_svgf_temporal(SvgfTemporalArgs a) {
                     const float4 h1 = a.ghist[2 * q + 1];
                     if (__float_as_int(h1.w) < 0) continue;
                     const float4 h0 = a.ghist[2 * q];
-                    const float pd = sv_dot(h0.x - g0.x, h0.y - g0.y, h0.z - g0.z, g1.x, g1.y, g1.z);
+                    const float pd = rp_dot(h0.x - g0.x, h0.y - g0.y, h0.z - g0.z, g1.x, g1.y, g1.z);
                     if (!(fabsf(pd) <= tol)) continue;
-                    const float nd = sv_dot(h1.x, h1.y, h1.z, g1.x, g1.y, g1.z);
+                    const float nd = rp_dot(h1.x, h1.y, h1.z, g1.x, g1.y, g1.z);
                     if (!(fabsf(nd) >= a.normal_cos)) continue;
                     const float4 hq = a.hin[q];
                     sw = sw + w;
@@ -200,9 +175,9 @@ __global__ __launch_bounds__(256) void k_svgf_variance(SvgfVarianceArgs a) {
                     if (hit_p != hit_q) continue;
                     if (hit_p) {
                         const float4 q0 = a.geo[2 * q];
-                        const float pd = sv_dot(q0.x - g0.x, q0.y - g0.y, q0.z - g0.z, g1.x, g1.y, g1.z);
+                        const float pd = rp_dot(q0.x - g0.x, q0.y - g0.y, q0.z - g0.z, g1.x, g1.y, g1.z);
                         if (!(fabsf(pd) <= tol)) continue;
-                        const float nd = sv_dot(q1.x, q1.y, q1.z, g1.x, g1.y, g1.z);
+                        const float nd = rp_dot(q1.x, q1.y, q1.z, g1.x, g1.y, g1.z);
                         if (!(fabsf(nd) >= a.normal_cos)) continue;
                     }
                 }
@@ -302,7 +277,7 @@ __global__ __launch_bounds__(256, 8) void k_svgf_atrous(SvgfFilterArgs a) {
                 // a miss carries t = FLT_MAX in the guide: the hit flag of q without its second record. Selects,
                 // not branches: a lane that fails the test keeps the wave's pace
                 const bool hit_q = xq.w < RTG_FLT_MAX;
-                const float pd = sv_dot(xq.x - xp.x, xq.y - xp.y, xq.z - xp.z, np.x, np.y, np.z);
+                const float pd = rp_dot(xq.x - xp.x, xq.y - xp.y, xq.z - xp.z, np.x, np.y, np.z);
                 const bool pass = (dy == 0 && dx == 0) || (hit_p == hit_q && (!hit_p || fabsf(pd) <= tol));
                 w = pass ? w : 0.0f;
             }
@@ -329,29 +304,19 @@ __global__ __launch_bounds__(256) void k_svgf_unpack(const float4* __restrict__ 
 }
 
 // ------------------------------------------------------------------ host side
-void svgf_release(TemporalState& t) {
-    SvgfState* s = t.sv;
-    if (!s) return;
-    (void)hipFree(s->mom[0]); (void)hipFree(s->mom[1]); (void)hipFree(s->col[0]); (void)hipFree(s->col[1]);
-    (void)hipFree(s->var); (void)hipFree(s->out); (void)hipFree(s->xpos);
-    for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
-    delete s;
-    t.sv = nullptr;
-}
-
-// the temporal state's svgf buffers, allocated on first use
-static int ensure_state(TemporalState& t) {
+// The temporal state's variance-guided part, built on first use: a local one, handed to t by the last statement
+// (a failed allocation leaves t.sv null and the next call builds again). t's destructor frees it.
+static int build_state(TemporalState& t) {
     if (t.sv) return RTG_OK;
-    t.sv = new SvgfState();
-    SvgfState& s = *t.sv;
-    for (auto& e : s.ev) HIPOK(hipEventCreate(&e));
-    HIPOK(hipMalloc((void**)&s.mom[0], t.n * sizeof(float2)));
-    HIPOK(hipMalloc((void**)&s.mom[1], t.n * sizeof(float2)));
-    HIPOK(hipMalloc((void**)&s.col[0], t.n * sizeof(float4)));
-    HIPOK(hipMalloc((void**)&s.col[1], t.n * sizeof(float4)));
-    HIPOK(hipMalloc((void**)&s.var, t.n * sizeof(float)));
-    HIPOK(hipMalloc((void**)&s.xpos, t.n * sizeof(float4)));
-    HIPOK(hipMalloc((void**)&s.out, 3 * t.n * sizeof(float)));
+    auto s = std::make_unique<SvgfState>();
+    if (int rc = s->ev.create()) return rc;
+    for (DevBuf<float2>& b : s->mom)
+        if (int rc = b.alloc(t.n)) return rc;
+    for (DevBuf<float4>* b : {&s->col[0], &s->col[1], &s->xpos})
+        if (int rc = b->alloc(t.n)) return rc;
+    if (int rc = s->var.alloc(t.n)) return rc;
+    if (int rc = s->out.alloc(3 * t.n)) return rc;
+    t.sv = std::move(s);
     return RTG_OK;
 }
 
@@ -375,7 +340,7 @@ static int svgf_check(const char* who, const rtg_svgf_params* p) {
 static SvgfState* result_state(const char* who, rtg_handle* h) {
     if (!h) { g_err = std::string(who) + ": null argument"; return nullptr; }
     if (!h->tp || !h->tp->sv || !h->tp->sv->have_result) { g_err = std::string(who) + ": no result yet"; return nullptr; }
-    return h->tp->sv;
+    return h->tp->sv.get();
 }
 
 extern "C" {
@@ -401,42 +366,24 @@ int rtg_svgf_accumulate(rtg_handle* h, const rtg_svgf_params* p, float* out) {
     if (int rc = settle(h)) return rc;  // the film holds every queued frame, and slot 0's buffers are free
     if (int rc = temporal_state("rtg_svgf_accumulate", h)) return rc;
     TemporalState& t = *h->tp;
-    if (int rc = ensure_state(t)) return rc;
+    if (int rc = build_state(t)) return rc;
     if (int rc = denoise_state(h)) return rc;
     SvgfState& s = *t.sv;
     hipStream_t st = h->stream;
     const dim3 grid((unsigned)(h->W + 63) / 64, (unsigned)(h->H + 3) / 4);
-    const bool unchanged = t.have_hist && same_camera(h->cam, h->proj, t.hcam, t.hproj);
+    SvgfTemporalArgs a{};
+    const bool unchanged = temporal_setup(h, t, p->temporal, a);
+    a.mom_on = (t.have_hist && s.mom_valid) ? 1 : 0;
+    a.mom_in = s.mom[s.cur].p;
+    a.mom_out = s.mom[s.cur ^ 1].p;
     const float4* g = nullptr;  // the current geometry guide: the history's own when the camera is its camera
     bool traced = false;
     HIPOK(hipEventRecord(s.ev[0], st));
     // one fused first-hit pass for the geometry guide and the denoiser's guides (nothing when both are at hand);
     // it renders nothing, so the statistics have nothing to be put back
-    if (int rc = current_gbuffer(h, &g, &traced)) return rc;
+    if (int rc = current_guide(h, true, &g, &traced)) return rc;
     HIPOK(hipEventRecord(s.ev[1], st));
-
-    SvgfTemporalArgs a{};
-    a.film = h->d_film;
-    a.m = (float)h->spp;
-    a.hin = t.hist[t.cur];
-    a.hout = t.hist[t.cur ^ 1];
-    a.mom_in = s.mom[s.cur];
-    a.mom_out = s.mom[s.cur ^ 1];
-    a.W = h->W;
-    a.H = h->H;
-    a.max_history = p->temporal.max_history;
-    a.plane_tolerance = p->temporal.plane_tolerance;
-    a.normal_cos = p->temporal.normal_cos;
-    a.mode = !t.have_hist ? 0 : (unchanged ? 1 : 2);
-    a.mom_on = (t.have_hist && s.mom_valid) ? 1 : 0;
-    if (a.mode == 2) {
-        a.gcur = g;
-        a.ghist = t.hguide;
-        std::memcpy(a.cam.P, t.hproj.proj, sizeof(a.cam.P));
-        std::memcpy(a.cam.C2V, t.hproj.camera_to_view, sizeof(a.cam.C2V));
-        a.cam.W = t.hcam.width;
-        a.cam.H = t.hcam.height;
-    }
+    if (a.mode == 2) a.gcur = g;
     HIPOK(hipEventRecord(s.ev[2], st));
     hipLaunchKernelGGL(k_svgf_temporal, grid, dim3(256), 0, st, a);
     LAUNCH_OK("k_svgf_temporal");
@@ -446,8 +393,8 @@ int rtg_svgf_accumulate(rtg_handle* h, const rtg_svgf_params* p, float* out) {
     v.hist = a.hout;
     v.mom = a.mom_out;
     v.geo = g;
-    v.col = s.col[0];
-    v.var = s.var;
+    v.col = s.col[0].p;
+    v.var = s.var.p;
     v.W = h->W;
     v.H = h->H;
     v.min_history = p->min_history;
@@ -458,12 +405,12 @@ int rtg_svgf_accumulate(rtg_handle* h, const rtg_svgf_params* p, float* out) {
     HIPOK(hipEventRecord(s.ev[4], st));
 
     const dim3 lin((unsigned)((t.n + 255) / 256));
-    hipLaunchKernelGGL(k_svgf_pack_pos, lin, dim3(256), 0, st, g, t.n, s.xpos);
+    hipLaunchKernelGGL(k_svgf_pack_pos, lin, dim3(256), 0, st, g, t.n, s.xpos.p);
     LAUNCH_OK("k_svgf_pack_pos");
     SvgfFilterArgs f{};
-    f.guide = h->dn->guide;
+    f.guide = h->dn->guide.p;
     f.geo = g;
-    f.xpos = s.xpos;
+    f.xpos = s.xpos.p;
     f.W = h->W;
     f.H = h->H;
     f.m = (int)p->normal_squarings;
@@ -473,20 +420,20 @@ int rtg_svgf_accumulate(rtg_handle* h, const rtg_svgf_params* p, float* out) {
     f.ia = f.alb_on ? 1.0f / (p->sigma_albedo * p->sigma_albedo) : 0.0f;
     f.plane_tolerance = p->temporal.plane_tolerance;
     for (uint32_t i = 0; i < p->iterations; ++i) {
-        f.cin = s.col[i & 1];
-        f.cout = s.col[(i + 1) & 1];
+        f.cin = s.col[i & 1].p;
+        f.cout = s.col[(i + 1) & 1].p;
         f.step = 1 << i;
         hipLaunchKernelGGL(k_svgf_atrous, grid, dim3(256), 0, st, f);
         LAUNCH_OK("k_svgf_atrous");
     }
     HIPOK(hipEventRecord(s.ev[5], st));
     hipLaunchKernelGGL(k_svgf_unpack, lin, dim3(256), 0, st,
-                       (const float4*)s.col[p->iterations & 1], t.n, s.out);
+                       (const float4*)s.col[p->iterations & 1].p, t.n, s.out.p);
     LAUNCH_OK("k_svgf_unpack");
-    if (out) HIPOK(hipMemcpyAsync(out, s.out, t.n * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (out) HIPOK(hipMemcpyAsync(out, s.out.p, t.n * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
     HIPOK(hipStreamSynchronize(st));
     float ms = 0.0f;
-    s.guide_ms = (traced && hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) == hipSuccess) ? ms : 0.0;
+    s.guide_ms = stage_ms(traced, s.ev[0], s.ev[1]);
     t.gbuffer_ms = s.guide_ms;
     if (hipEventElapsedTime(&ms, s.ev[2], s.ev[3]) == hipSuccess) s.accumulate_ms = ms;
     if (hipEventElapsedTime(&ms, s.ev[3], s.ev[4]) == hipSuccess) s.variance_ms = ms;
@@ -503,7 +450,7 @@ int rtg_svgf_variance(rtg_handle* h, float* var) {
     if (!s) return RTG_ERR_ARG;
     HIPOK(hipSetDevice(h->device));
     HIPOK(hipStreamSynchronize(h->stream));
-    HIPOK(hipMemcpy(var, s->var, h->tp->n * sizeof(float), hipMemcpyDeviceToHost));
+    HIPOK(hipMemcpy(var, s->var.p, h->tp->n * sizeof(float), hipMemcpyDeviceToHost));
     return RTG_OK;
 }
 
@@ -513,22 +460,18 @@ int rtg_svgf_moments(rtg_handle* h, float* mu) {
     if (!s->mom_valid) { g_err = "rtg_svgf_moments: the moments were dropped by rtg_temporal_accumulate"; return RTG_ERR_ARG; }
     HIPOK(hipSetDevice(h->device));
     HIPOK(hipStreamSynchronize(h->stream));
-    HIPOK(hipMemcpy(mu, s->mom[s->cur], h->tp->n * sizeof(float2), hipMemcpyDeviceToHost));
+    HIPOK(hipMemcpy(mu, s->mom[s->cur].p, h->tp->n * sizeof(float2), hipMemcpyDeviceToHost));
     return RTG_OK;
 }
 
 int rtg_svgf_copy_device(rtg_handle* h, void* dst_device) {
-    SvgfState* s = result_state("rtg_svgf_copy_device", dst_device ? h : nullptr);
-    if (!s) return RTG_ERR_ARG;
-    HIPOK(hipSetDevice(h->device));
-    HIPOK(hipMemcpyAsync(dst_device, s->out, h->tp->n * 3 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    HIPOK(hipStreamSynchronize(h->stream));
-    return RTG_OK;
+    const bool have = h && h->tp && h->tp->sv && h->tp->sv->have_result;
+    return copy_result("rtg_svgf_copy_device", h, have ? h->tp->sv->out.p : nullptr, dst_device);
 }
 
 int rtg_svgf_ms(rtg_handle* h, double* guide_ms, double* accumulate_ms, double* variance_ms, double* filter_ms) {
     if (!h) { g_err = "rtg_svgf_ms: null handle"; return RTG_ERR_ARG; }
-    const SvgfState* s = (h->tp && h->tp->sv) ? h->tp->sv : nullptr;
+    const SvgfState* s = h->tp ? h->tp->sv.get() : nullptr;
     if (guide_ms) *guide_ms = s ? s->guide_ms : 0.0;
     if (accumulate_ms) *accumulate_ms = s ? s->accumulate_ms : 0.0;
     if (variance_ms) *variance_ms = s ? s->variance_ms : 0.0;

@@ -18,7 +18,7 @@
 // film's three floats and at most 4 x 3 tap loads; it writes one history record and three floats.
 // Blocks are 64 x 4 pixels with a wave on 64 consecutive x of one row, as k_dn_atrous lays them out.
 // No atomics; no address depends on a colour (the tap addresses depend on geometry alone).
-#include "rtg_filter_state.h"
+#include "rtg_reproject.h"
 
 #include <cmath>
 #include <cstring>
@@ -67,31 +67,6 @@ __global__ __launch_bounds__(256) void k_geometry_guide(const DevTri48* __restri
     guide[2 * (size_t)pixel + 1] = g1;
 }
 
-static __device__ __forceinline__ float tp_dot(float ax, float ay, float az, float bx, float by, float bz) {
-    return (ax * bx + ay * by) + az * bz;
-}
-
-// Camera::projectOntoCamera (Scene.h:55-69) in project_onto_camera's operation order (rtg_light.hip)
-static __device__ __forceinline__ bool tp_project(const TemporalProj& c, float px, float py, float pz, float& x,
-                                                  float& y) {
-    const float* m = c.C2V;
-    const float vx = ((px * m[0] + py * m[1]) + pz * m[2]) + m[3];
-    const float vy = ((px * m[4] + py * m[5]) + pz * m[6]) + m[7];
-    const float vz = ((px * m[8] + py * m[9]) + pz * m[10]) + m[11];
-    const float* q = c.P;
-    const float v1x = ((vx * q[0] + vy * q[1]) + vz * q[2]) + q[3];
-    const float v1y = ((vx * q[4] + vy * q[5]) + vz * q[6]) + q[7];
-    float w = (((q[12] * vx) + (q[13] * vy)) + (q[14] * vz)) + q[15];
-    w = 1.0f / w;
-    x = ((v1x * w) + 1.0f) * 0.5f;
-    y = ((v1y * w) + 1.0f) * 0.5f;
-    if (x < 0 || x > 1.0f || y < 0 || y > 1.0f) return false;
-    x = x * c.W;
-    y = 1.0f - y;
-    y = y * c.H;
-    return true;
-}
-
 __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
     const int x = (int)blockIdx.x * 64 + (int)(threadIdx.x & 63u);
     const int y = (int)blockIdx.y * 4 + (int)(threadIdx.x >> 6);
@@ -106,7 +81,7 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
     } else if (a.mode == 2) {
         const float4 g0 = a.gcur[2 * p], g1 = a.gcur[2 * p + 1];
         float fx, fy;
-        if (__float_as_int(g1.w) >= 0 && tp_project(a.cam, g0.x, g0.y, g0.z, fx, fy)) {
+        if (__float_as_int(g1.w) >= 0 && rp_project(a.cam, g0.x, g0.y, g0.z, fx, fy)) {
             const float u = fx - 0.5f, v = fy - 0.5f;
             const float x0 = floorf(u), y0 = floorf(v);
             const float ax = u - x0, ay = v - y0;
@@ -127,9 +102,9 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
                     const float4 h1 = a.ghist[2 * q + 1];
                     if (__float_as_int(h1.w) < 0) continue;
                     const float4 h0 = a.ghist[2 * q];
-                    const float pd = tp_dot(h0.x - g0.x, h0.y - g0.y, h0.z - g0.z, g1.x, g1.y, g1.z);
+                    const float pd = rp_dot(h0.x - g0.x, h0.y - g0.y, h0.z - g0.z, g1.x, g1.y, g1.z);
                     if (!(fabsf(pd) <= tol)) continue;
-                    const float nd = tp_dot(h1.x, h1.y, h1.z, g1.x, g1.y, g1.z);
+                    const float nd = rp_dot(h1.x, h1.y, h1.z, g1.x, g1.y, g1.z);
                     if (!(fabsf(nd) >= a.normal_cos)) continue;
                     const float4 hq = a.hin[q];
                     sw = sw + w;
@@ -159,37 +134,32 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
 
 // ------------------------------------------------------------------ host side
 void temporal_release(rtg_handle* h) {
-    TemporalState* t = h->tp;
-    if (!t) return;
-    (void)hipFree(t->hist[0]); (void)hipFree(t->hist[1]); (void)hipFree(t->hguide);
-    (void)hipFree(t->cguide); (void)hipFree(t->out);
-    for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
-    svgf_release(*t);
-    delete t;
+    delete h->tp;  // (its buffers, its events and the variance-guided state with it)
     h->tp = nullptr;
 }
 
-static int check_size(const char* who, const rtg_handle* h) {
-    if (h->W <= 0 || h->H <= 0 || h->W > 65535 || h->H > 65535 || (uint64_t)h->W * h->H > (1ull << 28)) {
-        g_err = std::string(who) + ": the film must be 1..65535 per side and at most 2^28 pixels";
+int check_size(const char* who, int64_t W, int64_t H, const char* what) {
+    if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || W * H > (1ll << 28)) {
+        g_err = std::string(who) + ": " + what + " must be 1..65535 per side and at most 2^28 pixels";
         return RTG_ERR_ARG;
     }
     return RTG_OK;
 }
 
-// the handle's temporal state, allocated on first use
-static int ensure_state(rtg_handle* h) {
+// The handle's temporal state, built on first use: a local one, handed to the handle by the last statement, so
+// a failed allocation leaves the handle without one and the next call builds again.
+static int build_state(rtg_handle* h) {
     if (h->tp) return RTG_OK;
-    h->tp = new TemporalState();
-    TemporalState& t = *h->tp;
+    auto t = std::make_unique<TemporalState>();
     const size_t n = (size_t)h->W * h->H;
-    for (auto& e : t.ev) HIPOK(hipEventCreate(&e));
-    HIPOK(hipMalloc((void**)&t.hist[0], n * sizeof(float4)));
-    HIPOK(hipMalloc((void**)&t.hist[1], n * sizeof(float4)));
-    HIPOK(hipMalloc((void**)&t.hguide, 2 * n * sizeof(float4)));
-    HIPOK(hipMalloc((void**)&t.cguide, 2 * n * sizeof(float4)));
-    HIPOK(hipMalloc((void**)&t.out, 3 * n * sizeof(float)));
-    t.n = n;
+    if (int rc = t->ev.create()) return rc;
+    for (DevBuf<float4>* b : {&t->hist[0], &t->hist[1]})
+        if (int rc = b->alloc(n)) return rc;
+    for (DevBuf<float4>* b : {&t->hguide, &t->cguide})
+        if (int rc = b->alloc(2 * n)) return rc;
+    if (int rc = t->out.alloc(3 * n)) return rc;
+    t->n = n;
+    h->tp = t.release();
     return RTG_OK;
 }
 
@@ -243,67 +213,74 @@ static int trace_first_hits(rtg_handle* h, PathBufs** out) {
     return RTG_OK;
 }
 
-// The guide of the handle's camera, on h's stream (no host wait): the history's own when the camera is
-// its camera, the cache's when it holds this camera, else traced into the cache (trace_first_hits, then
-// k_geometry_guide).
-int current_guide(rtg_handle* h, const float4** guide, bool* traced) {
+// The guide of the handle's camera, on h's stream (no host wait): the history's own when the camera is its
+// camera, the cache's when it holds this camera, else traced into the cache (trace_first_hits, then
+// k_geometry_guide). with_denoiser: the denoiser's albedo / shading-normal guides with it (rtg_gbuffer.hip,
+// DESIGN.md 8k). Then nothing runs only when the geometry guide is at hand and the denoiser's guides are ready
+// as well; otherwise the one pass is trace_first_hits, then k_gbuffer into the guide cache and the denoiser's three
+// guide buffers, and both caches are valid for this camera. Without it h->dn is not looked at (it may be null).
+// The camera rays are traced once; the film, Film::SPP, the integrator, the options, the statistics, launch_ms /
+// launch_rays and the camera-sampling record are not touched. The caller has joined the queued frames, waited
+// for the stream, and built the states it asks for (temporal_state; denoise_state for with_denoiser).
+int current_guide(rtg_handle* h, bool with_denoiser, const float4** guide, bool* traced) {
     TemporalState& t = *h->tp;
+    DenoiseState* d = with_denoiser ? h->dn : nullptr;
     *traced = false;
-    if (t.have_hist && same_camera(h->cam, h->proj, t.hcam, t.hproj)) { *guide = t.hguide; return RTG_OK; }
-    if (t.cache_ready && same_camera(h->cam, h->proj, t.ccam, t.cproj)) { *guide = t.cguide; return RTG_OK; }
+    const bool own = t.have_hist && same_camera(h->cam, h->proj, t.hcam, t.hproj);
+    const bool cached = t.cache_ready && same_camera(h->cam, h->proj, t.ccam, t.cproj);
+    if ((own || cached) && (!d || d->guides_ready)) { *guide = own ? t.hguide.p : t.cguide.p; return RTG_OK; }
     t.cache_ready = false;
+    if (d) d->guides_ready = false;
     PathBufs* pb = nullptr;
     if (int rc = trace_first_hits(h, &pb)) return rc;
-    hipLaunchKernelGGL(k_geometry_guide, dim3((h->npix + 255) / 256), dim3(256), 0, h->stream, h->sv.tris48,
-                       (const unsigned*)h->d_pix, h->npix, (const float4*)pb->hits, (const float4*)pb->ray_d, h->cam.ox,
-                       h->cam.oy, h->cam.oz, t.cguide);
-    LAUNCH_OK("k_geometry_guide");
+    if (d) {
+        if (int rc = launch_gbuffer(h, *pb, t.cguide.p, *d, h->stream)) return rc;
+    } else {
+        hipLaunchKernelGGL(k_geometry_guide, dim3((h->npix + 255) / 256), dim3(256), 0, h->stream, h->sv.tris48,
+                           (const unsigned*)h->d_pix, h->npix, (const float4*)pb->hits, (const float4*)pb->ray_d,
+                           h->cam.ox, h->cam.oy, h->cam.oz, t.cguide.p);
+        LAUNCH_OK("k_geometry_guide");
+    }
     t.ccam = h->cam;
     t.cproj = h->proj;
     t.cache_ready = true;
-    *guide = t.cguide;
+    if (d) d->guides_ready = true;
+    *guide = own ? t.hguide.p : t.cguide.p;  // (the same bits; the history keeps its own buffer)
     *traced = true;
     return RTG_OK;
 }
 
-// The guide of the handle's camera as current_guide gives it, and the denoiser's albedo / shading-normal guides
-// with it (rtg_gbuffer.hip). Nothing runs when the geometry guide is at hand (the history's own
-// or the cache's) and the denoiser's guides are ready. Otherwise one pass on h's stream (no host wait):
-// trace_first_hits, then k_gbuffer into the guide cache and the denoiser's three guide buffers, and both caches
-// are valid for this camera. The camera rays are traced once; the film, Film::SPP, the integrator, the options,
-// the statistics, launch_ms / launch_rays and the camera-sampling record are not touched. The caller has joined
-// the queued frames, waited for the stream, and allocated both states (temporal_state, denoise_state).
-int current_gbuffer(rtg_handle* h, const float4** guide, bool* traced) {
-    TemporalState& t = *h->tp;
-    DenoiseState& d = *h->dn;
-    *traced = false;
-    const bool own = t.have_hist && same_camera(h->cam, h->proj, t.hcam, t.hproj);
-    const bool cached = t.cache_ready && same_camera(h->cam, h->proj, t.ccam, t.cproj);
-    if ((own || cached) && d.guides_ready) { *guide = own ? t.hguide : t.cguide; return RTG_OK; }
-    t.cache_ready = false;
-    d.guides_ready = false;
-    PathBufs* pb = nullptr;
-    if (int rc = trace_first_hits(h, &pb)) return rc;
-    if (int rc = launch_gbuffer(h, *pb, t.cguide, d, h->stream)) return rc;
-    t.ccam = h->cam;
-    t.cproj = h->proj;
-    t.cache_ready = true;
-    d.guides_ready = true;
-    *guide = own ? t.hguide : t.cguide;  // (the same bits; the history keeps its own buffer)
-    *traced = true;
+int download_guide(const rtg_handle* h, const float4* guide, float* pos_t, float* normal_id) {
+    if (!pos_t && !normal_id) return RTG_OK;
+    const size_t n = (size_t)h->W * h->H;
+    std::vector<float4> rec(2 * n);  // the two halves of a record go to the caller's two images
+    HIPOK(hipMemcpy(rec.data(), guide, rec.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+        if (pos_t) std::memcpy(pos_t + 4 * i, &rec[2 * i], sizeof(float4));
+        if (normal_id) std::memcpy(normal_id + 4 * i, &rec[2 * i + 1], sizeof(float4));
+    }
+    return RTG_OK;
+}
+
+int copy_result(const char* who, rtg_handle* h, const float* result, void* dst_device, const char* none) {
+    if (!h || !dst_device) { g_err = std::string(who) + ": null argument"; return RTG_ERR_ARG; }
+    if (!result) { g_err = std::string(who) + ": " + none; return RTG_ERR_ARG; }
+    HIPOK(hipSetDevice(h->device));
+    HIPOK(hipMemcpyAsync(dst_device, result, (size_t)h->W * h->H * 3 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    HIPOK(hipStreamSynchronize(h->stream));
     return RTG_OK;
 }
 
 int temporal_state(const char* who, rtg_handle* h) {
-    if (int rc = check_size(who, h)) return rc;
-    return ensure_state(h);
+    if (int rc = check_size(who, h->W, h->H)) return rc;
+    return build_state(h);
 }
 
 void temporal_advance(rtg_handle* h, bool unchanged, const float4* g) {
     TemporalState& t = *h->tp;
     t.cur ^= 1;
     if (!unchanged) {  // the stored camera and guide become the current ones
-        if (g == t.cguide) {
+        if (g == t.cguide.p) {
             // the cache's buffer becomes the history's; the history's old guide stays cached under its camera
             std::swap(t.hguide, t.cguide);
             const bool was = t.have_hist;
@@ -343,75 +320,46 @@ int rtg_temporal_check(const rtg_temporal_params* p) { return temporal_check("rt
 
 int rtg_geometry_guide(rtg_handle* h, float* pos_t, float* normal_id) {
     if (!h) { g_err = "rtg_geometry_guide: null handle"; return RTG_ERR_ARG; }
-    if (int rc = check_size("rtg_geometry_guide", h)) return rc;
+    if (int rc = check_size("rtg_geometry_guide", h->W, h->H)) return rc;
     if (int rc = settle(h)) return rc;  // slot 0's buffers are free
-    if (int rc = ensure_state(h)) return rc;
+    if (int rc = build_state(h)) return rc;
     TemporalState& t = *h->tp;
     const float4* g = nullptr;
     bool traced = false;
     HIPOK(hipEventRecord(t.ev[0], h->stream));
-    if (int rc = current_guide(h, &g, &traced)) return rc;
+    if (int rc = current_guide(h, false, &g, &traced)) return rc;
     HIPOK(hipEventRecord(t.ev[1], h->stream));
     HIPOK(hipStreamSynchronize(h->stream));
-    float ms = 0.0f;
-    t.guide_ms = (traced && hipEventElapsedTime(&ms, t.ev[0], t.ev[1]) == hipSuccess) ? ms : 0.0;
-    if (!pos_t && !normal_id) return RTG_OK;
-    std::vector<float4> rec(2 * t.n);  // the two halves of a record go to the caller's two images
-    HIPOK(hipMemcpy(rec.data(), g, rec.size() * sizeof(float4), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < t.n; ++i) {
-        if (pos_t) std::memcpy(pos_t + 4 * i, &rec[2 * i], sizeof(float4));
-        if (normal_id) std::memcpy(normal_id + 4 * i, &rec[2 * i + 1], sizeof(float4));
-    }
-    return RTG_OK;
+    t.guide_ms = stage_ms(traced, t.ev[0], t.ev[1]);
+    return download_guide(h, g, pos_t, normal_id);
 }
 
 int rtg_temporal_accumulate(rtg_handle* h, const rtg_temporal_params* p, float* out) {
     if (!h) { g_err = "rtg_temporal_accumulate: null handle"; return RTG_ERR_ARG; }
     if (int rc = temporal_check("rtg_temporal_accumulate", p)) return rc;
     if (h->spp == 0) { g_err = "rtg_temporal_accumulate: the film holds no samples (spp == 0)"; return RTG_ERR_ARG; }
-    if (int rc = check_size("rtg_temporal_accumulate", h)) return rc;
+    if (int rc = check_size("rtg_temporal_accumulate", h->W, h->H)) return rc;
     if (int rc = settle(h)) return rc;  // the film holds every queued frame, and slot 0's buffers are free
-    if (int rc = ensure_state(h)) return rc;
+    if (int rc = build_state(h)) return rc;
     TemporalState& t = *h->tp;
     TemporalArgs a{};
-    a.film = h->d_film;
-    a.m = (float)h->spp;
-    a.hin = t.hist[t.cur];
-    a.hout = t.hist[t.cur ^ 1];
-    a.out = t.out;
-    a.W = h->W;
-    a.H = h->H;
-    a.max_history = p->max_history;
-    a.plane_tolerance = p->plane_tolerance;
-    a.normal_cos = p->normal_cos;
-    const bool unchanged = t.have_hist && same_camera(h->cam, h->proj, t.hcam, t.hproj);
+    const bool unchanged = temporal_setup(h, t, *p, a);
+    a.out = t.out.p;
     const float4* g = nullptr;
     bool traced = false;
     HIPOK(hipEventRecord(t.ev[0], h->stream));
-    if (!unchanged)
-        if (int rc = current_guide(h, &g, &traced)) return rc;
+    if (!unchanged)  // (the denoiser's guides are not this call's: h->dn may not exist)
+        if (int rc = current_guide(h, false, &g, &traced)) return rc;
     HIPOK(hipEventRecord(t.ev[1], h->stream));
-    if (!t.have_hist) {
-        a.mode = 0;
-    } else if (unchanged) {
-        a.mode = 1;
-    } else {
-        a.mode = 2;
-        a.gcur = g;
-        a.ghist = t.hguide;
-        std::memcpy(a.cam.P, t.hproj.proj, sizeof(a.cam.P));
-        std::memcpy(a.cam.C2V, t.hproj.camera_to_view, sizeof(a.cam.C2V));
-        a.cam.W = t.hcam.width;
-        a.cam.H = t.hcam.height;
-    }
+    if (a.mode == 2) a.gcur = g;
     HIPOK(hipEventRecord(t.ev[2], h->stream));
     hipLaunchKernelGGL(k_temporal, dim3((unsigned)(h->W + 63) / 64, (unsigned)(h->H + 3) / 4), dim3(256), 0, h->stream, a);
     LAUNCH_OK("k_temporal");
     HIPOK(hipEventRecord(t.ev[3], h->stream));
-    if (out) HIPOK(hipMemcpyAsync(out, t.out, t.n * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (out) HIPOK(hipMemcpyAsync(out, t.out.p, t.n * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPOK(hipStreamSynchronize(h->stream));
     float ms = 0.0f;
-    t.guide_ms = (traced && hipEventElapsedTime(&ms, t.ev[0], t.ev[1]) == hipSuccess) ? ms : 0.0;
+    t.guide_ms = stage_ms(traced, t.ev[0], t.ev[1]);
     if (hipEventElapsedTime(&ms, t.ev[2], t.ev[3]) == hipSuccess) t.accumulate_ms = ms;
     temporal_advance(h, unchanged, g);
     if (t.sv) t.sv->mom_valid = false;  // the moments history of rtg_svgf_accumulate no longer belongs to H
@@ -424,17 +372,13 @@ int rtg_temporal_history(rtg_handle* h, float* rgb_len) {
     if (!h->tp || !h->tp->have_hist) { g_err = "rtg_temporal_history: no history yet"; return RTG_ERR_ARG; }
     HIPOK(hipSetDevice(h->device));
     HIPOK(hipStreamSynchronize(h->stream));
-    HIPOK(hipMemcpy(rgb_len, h->tp->hist[h->tp->cur], h->tp->n * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPOK(hipMemcpy(rgb_len, h->tp->hist[h->tp->cur].p, h->tp->n * sizeof(float4), hipMemcpyDeviceToHost));
     return RTG_OK;
 }
 
 int rtg_temporal_copy_device(rtg_handle* h, void* dst_device) {
-    if (!h || !dst_device) { g_err = "rtg_temporal_copy_device: null argument"; return RTG_ERR_ARG; }
-    if (!h->tp || !h->tp->have_result) { g_err = "rtg_temporal_copy_device: no result yet"; return RTG_ERR_ARG; }
-    HIPOK(hipSetDevice(h->device));
-    HIPOK(hipMemcpyAsync(dst_device, h->tp->out, h->tp->n * 3 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    HIPOK(hipStreamSynchronize(h->stream));
-    return RTG_OK;
+    const bool have = h && h->tp && h->tp->have_result;
+    return copy_result("rtg_temporal_copy_device", h, have ? h->tp->out.p : nullptr, dst_device);
 }
 
 int rtg_temporal_reset(rtg_handle* h) {

@@ -41,7 +41,8 @@ extern "C" {
  *    (additive, still 6: the denoiser, rtg_denoise_* and rtg_group_denoise; camera sampling,
  *    rtg_*_camera_sampling and rtg_probe_camera_samples; environment light sampling,
  *    rtg_*_env_sampling, rtg_env_* and rtg_probe_env_samples; rtg_probe_connect; light selection,
- *    rtg_*_light_sampling, rtg_light_* and rtg_probe_light_pick; the material model,
+ *    rtg_*_light_sampling, rtg_light_* and rtg_probe_light_pick; its per-cell refinement,
+ *    rtg_*_light_grid, rtg_light_grid_* and rtg_probe_light_grid; the material model,
  *    rtg_*_material_model, rtg_*_material_params and rtg_probe_material; path-tracer MIS,
  *    rtg_*_path_mis, rtg_probe_mis_weight, rtg_probe_env_pdf and rtg_light_of_triangle; rough dielectric
  *    transmission, RTG_MODEL_ROUGH_DIELECTRIC and rtg_probe_transmission; a movable camera, rtg_*_camera;
@@ -403,6 +404,82 @@ int  rtg_probe_light_pick(rtg_handle* h, const uint32_t* r0, const float* d1, ui
 int  rtg_light_pick_build(const double* weights, uint32_t n, double uniform_share, double* pmf, double* prob,
                           uint32_t* alias, float* entries);
 
+/* ---- per-shading-point light selection (rtg_light_grid.hip). RTG_LIGHTS_POWER's pmf is the
+ * same at every shading point. rtg_set_light_grid refines it: with RTG_LIGHTS_POWER active and cells != 0,
+ * the pmf of a pick is the one of the grid cell that holds the shading point, through one alias table per
+ * cell in §8d's 16-byte format, so the pick stays one 16-byte load whose base address alone depends on the
+ * point. Default off (cells = 0): nothing changes unless rtg_set_light_grid is called.
+ * Definition, for a light list of n entries and lambda = (double)uniform_share of rtg_set_light_sampling:
+ *   grid           the box is the reference root box, six float32 values widened to binary64, lo_a, hi_a,
+ *                  e_a = hi_a - lo_a per axis a, E = the largest e_a. dims_a = max(1, (int)ceil((double)cells *
+ *                  (e_a / E))), and 1 on a degenerate axis (e_a not > 0; all three when E is not > 0). The
+ *                  kernel's constants are float32: lo_a as given, and scale_a = (float)dims_a / (hi_a - lo_a),
+ *                  one float32 subtraction and one float32 division, 0 on a degenerate axis.
+ *   cell of x      device, float32, no contraction: u = (x_a - lo_a) * scale_a; i_a = (int)u clamped to
+ *                  [0, dims_a - 1], a NaN giving 0; c = (i_z * dims_y + i_y) * dims_x + i_x.
+ *   weights        host, binary64, the operations in the order written. w_i is §8d's weight of light i,
+ *                  unchanged. s_a = e_a / dims_a; cell (i_x, i_y, i_z) has the box clo_a = lo_a + i_a * s_a,
+ *                  chi_a = lo_a + (i_a + 1) * s_a.
+ *                  Area light: tlo_a, thi_a the smallest and largest of the a coordinates of the triangle's
+ *                  three float32 vertices; d_a = max(0, tlo_a - chi_a, clo_a - thi_a); d2 = (d_x*d_x +
+ *                  d_y*d_y) + d_z*d_z; r2 = 0.25 * ((s_x*s_x + s_y*s_y) + s_z*s_z); g = 1 / max(d2, r2).
+ *                  Facing: the emitter is one-sided. With the cell's box widened by s_a / 2 on every side
+ *                  (clo_a - s_a / 2, chi_a + s_a / 2), if none of its eight corners k has
+ *                  ((k_x - v0_x)*gn_x + (k_y - v0_y)*gn_y) + (k_z - v0_z)*gn_z > 0 (v0 and the geometric
+ *                  normal gn from the light record), then g = 0. The half cell of slack keeps a point that
+ *                  float32 arithmetic puts in a neighbouring cell from meeting a pmf that should not be zero
+ *                  at lambda = 0.
+ *                  Environment light: g = 1 / (R * R) in every cell, R as in §8d; its weight per cell is
+ *                  then 2 pi^2 S / N, on the footing of power over squared distance.
+ *                  w_ic = w_i * g.
+ *   per cell       pmf_ic = ((1 - lambda) * w_ic) / sum_c + lambda / n, sum_c = the w_ic added in light order.
+ *                  A cell whose sum is 0 or not finite gets the uniform table: prob 1, alias self, pmf
+ *                  (float)(1.0 / n). Otherwise §8d's Vose (rtg_env_alias.h, in its fixed order) on p_k =
+ *                  pmf_k * n. Entries {prob, alias, pmf_self, pmf_alias} at table[c * n + k].
+ *   pick           draws, order and count are the power pick's, r0 then d1: li = light_pick(table + c * n,
+ *                  n, r0, d1, pmf), c the cell of the hit point x the NEE sample is drawn for. Everything
+ *                  after the pick is unchanged; DIRECT_MIS keeps the reference's reuse of pdf * pmf of the
+ *                  sampled light (§8d).
+ * The setting is stored whatever the light mode; the tables are built when it and RTG_LIGHTS_POWER are both
+ * set and the power mode has a table (a fallback of §8d, one light or no power, leaves no grid either),
+ * rebuilt when cells or uniform_share changes, and kept until rtg_destroy. cells above 64, or a grid of more
+ * than 2^24 entries (dims_x * dims_y * dims_z * n_lights, 256 MB) for the handle's root box: RTG_ERR_ARG before
+ * any device call, the message naming the largest admissible cells, and the previous setting stays.
+ * rtg_light_grid_check has no scene and refuses what no box admits: cells above 64, or cells * n_lights (the
+ * thinnest grid, cells x 1 x 1) above 2^24. A build that fails on the device (RTG_ERR_HIP, from either
+ * setter) leaves no grid, and frames run the power pick. A hierarchy for
+ * longer light lists is not covered. rtg_set_light_grid first issues and waits for queued frames.
+ * It applies to rtg_render, rtg_render_async, rtg_render_adaptive and the group calls under
+ * RTG_INTEGRATOR_PATH, _DIRECT and _DIRECT_MIS with the reference material model and either environment
+ * mode (kernels of their own, k_shade_grid). A handle whose frames run k_shade_phys, k_shade_mis or
+ * k_shade_trans (RTG_MATERIALS_PHYSICAL with such a record, RTG_PATH_MIS_POWER under PATH) keeps the power
+ * pick and its one table: those kernels take their pick as a run-time argument, and a grid there would
+ * change them. Not covered either: rtg_render_light, rtg_render_instant_radiosity, the denoiser's guides. */
+typedef struct rtg_light_grid {
+    uint32_t cells;        /* 0: off (default); else 1..64 cells on the longest axis of the root box */
+} rtg_light_grid;
+int  rtg_light_grid_defaults(rtg_light_grid* p);  /* {0} */
+int  rtg_light_grid_check(const rtg_light_grid* p, uint32_t n_lights);  /* no device needed */
+int  rtg_set_light_grid(rtg_handle* h, const rtg_light_grid* p);
+int  rtg_get_light_grid(rtg_handle* h, rtg_light_grid* p);
+/* dims[3], lo[3], scale[3] as the kernel uses them; *n_entries = cells of the grid * n_lights (0: no grid
+ * is active, and the other outputs are 0); build_ms the host time of the last build. Any pointer but h may
+ * be NULL. */
+int  rtg_light_grid_info(rtg_handle* h, uint32_t* dims, float* lo, float* scale, uint64_t* n_entries, double* build_ms);
+/* The active tables, n_entries * 4 32-bit words. No active grid: RTG_ERR_ARG. */
+int  rtg_light_grid_table(rtg_handle* h, float* entries);
+/* The kernel's own cell and pick for n points (n*3) and scripted draws against the active grid: cell[n],
+ * li[n], pmf[n]. No active grid: RTG_ERR_ARG. */
+int  rtg_probe_light_grid(rtg_handle* h, const float* points, const uint32_t* r0, const float* d1, uint32_t n,
+                          int32_t* cell, int32_t* li, float* pmf);
+/* The host's builder alone, binary64, no device call: from n light records (rtg_light_records' layout),
+ * their §8d weights and the root box, dims[3], lo[3], scale[3] and (entries may be NULL, to learn dims
+ * first) the dims product * n * 4 words. n == 0, cells outside 1..64, more than 2^24 entries, uniform_share
+ * outside [0, 1] or NaN: RTG_ERR_ARG. */
+int  rtg_light_grid_build(const float* light_records, uint32_t n, const double* weights, const float* root_box,
+                          uint32_t cells, double uniform_share, uint32_t* dims, float* lo, float* scale,
+                          float* entries);
+
 /* ---- material model (rtg_shade_phys.hip, rtg_phys.h). RTBase's ConductorBSDF, PlasticBSDF
  * and OrenNayarBSDF are stubs that shade as a cosine-sampled Lambertian (RTG_MAT_LAMBERT), and
  * ShadingHelper::Dggx / lambdaGGX / Gggx return 1. That is the default here, RTG_MATERIALS_REFERENCE,
@@ -649,7 +726,7 @@ int  rtg_probe_transmission(const float* cases, uint32_t n, float* out);
  * to RTG_INTEGRATOR_DIRECT, _DIRECT_MIS, _ALBEDO and _NORMALS, to rtg_render_light and
  * rtg_render_instant_radiosity, or to the denoiser's guides: they keep today's kernels and bits under
  * either setting. A rough dielectric record (RTG_MODEL_ROUGH_DIELECTRIC) is covered: p_b is its PDF with both
- * lobes. Not covered: LayeredBSDF, per-shading-point light selection, a lower RTG_ALPHA_DELTA. The setter first issues and waits for queued frames; an unknown
+ * lobes. Not covered: LayeredBSDF, per-shading-point light selection (rtg_set_light_grid leaves this mode the power pick), a lower RTG_ALPHA_DELTA. The setter first issues and waits for queued frames; an unknown
  * mode is RTG_ERR_ARG, reported before any device call, with the setting and the film left as they were
  * (rtg_path_mis_check is that check alone). The triangle -> light map (int32 per triangle, -1: no light)
  * is built on the host from the light list when the mode is first switched on and kept until
@@ -944,6 +1021,7 @@ int  rtg_group_set_options(rtg_group* g, int max_depth, int flags, uint32_t max_
 int  rtg_group_set_camera_sampling(rtg_group* g, const rtg_camera_sampling* p);  /* every rank's handle */
 int  rtg_group_set_env_sampling(rtg_group* g, int mode);  /* rtg_set_env_sampling on every rank's handle */
 int  rtg_group_set_light_sampling(rtg_group* g, const rtg_light_sampling* p);  /* every rank's handle */
+int  rtg_group_set_light_grid(rtg_group* g, const rtg_light_grid* p);          /* every rank's handle */
 int  rtg_group_set_material_params(rtg_group* g, const rtg_material_params* params, uint32_t n);  /* every rank's */
 int  rtg_group_set_material_model(rtg_group* g, int mode);  /* rtg_set_material_model on every rank's handle */
 int  rtg_group_set_path_mis(rtg_group* g, int mode);  /* rtg_set_path_mis on every rank's handle */

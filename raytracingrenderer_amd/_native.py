@@ -87,6 +87,10 @@ class rtg_light_sampling(C.Structure):
     _fields_ = [("mode", C.c_int32), ("uniform_share", C.c_float)]
 
 
+class rtg_light_grid(C.Structure):
+    _fields_ = [("cells", C.c_uint32)]
+
+
 class rtg_material_params(C.Structure):
     _fields_ = [("model", C.c_int32), ("alpha", C.c_float), ("sigma", C.c_float), ("eta", C.c_float * 3),
                 ("k", C.c_float * 3), ("int_ior", C.c_float), ("ext_ior", C.c_float)]
@@ -202,6 +206,17 @@ RTG_EXPORTS = [
     ("rtg_probe_light_pick", C.c_int, [C.c_void_p, u32p, f32p, C.c_uint32, i32p, f32p]),
     ("rtg_light_pick_build", C.c_int, [C.POINTER(C.c_double), C.c_uint32, C.c_double, C.POINTER(C.c_double),
                                        C.POINTER(C.c_double), u32p, f32p]),
+    # per-shading-point light selection: one alias table per grid cell (rtg_light_grid.hip)
+    ("rtg_light_grid_defaults", C.c_int, [C.POINTER(rtg_light_grid)]),
+    ("rtg_light_grid_check", C.c_int, [C.POINTER(rtg_light_grid), C.c_uint32]),
+    ("rtg_set_light_grid", C.c_int, [C.c_void_p, C.POINTER(rtg_light_grid)]),
+    ("rtg_get_light_grid", C.c_int, [C.c_void_p, C.POINTER(rtg_light_grid)]),
+    ("rtg_group_set_light_grid", C.c_int, [C.c_void_p, C.POINTER(rtg_light_grid)]),
+    ("rtg_light_grid_info", C.c_int, [C.c_void_p, u32p, f32p, f32p, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    ("rtg_light_grid_table", C.c_int, [C.c_void_p, f32p]),
+    ("rtg_probe_light_grid", C.c_int, [C.c_void_p, f32p, u32p, f32p, C.c_uint32, i32p, i32p, f32p]),
+    ("rtg_light_grid_build", C.c_int, [f32p, C.c_uint32, C.POINTER(C.c_double), f32p, C.c_uint32, C.c_double, u32p,
+                                       f32p, f32p, f32p]),
     # the material model: physical conductor, plastic and Oren-Nayar (rtg_shade_phys.hip)
     ("rtg_material_params_check", C.c_int, [C.POINTER(rtg_material_params), C.c_uint32, C.c_uint32]),
     ("rtg_set_material_params", C.c_int, [C.c_void_p, C.POINTER(rtg_material_params), C.c_uint32]),

@@ -32,7 +32,8 @@ DEVICE_SRC = ["device/rtg_trace.hip", "device/rtg_scene.hip", "device/rtg_render
               "device/rtg_shade.hip", "device/rtg_light.hip", "device/rtg_multi.hip", "device/rtg_bvh.hip",
               "device/rtg_denoise.hip", "device/rtg_env.hip", "device/rtg_light_pick.hip",
               "device/rtg_shade_phys.hip", "device/rtg_shade_mis.hip", "device/rtg_shade_trans.hip",
-              "device/rtg_temporal.hip", "device/rtg_svgf.hip", "device/rtg_gbuffer.hip"]
+              "device/rtg_temporal.hip", "device/rtg_svgf.hip", "device/rtg_gbuffer.hip",
+              "device/rtg_light_grid.hip"]
 # per-unit compile flags: k_shade's translation unit takes LLVM's max-ilp scheduler, which its
 # latency-bound body prefers, while the traversal keeps the default; the traversal's
 # unit is built without SLP vectorisation, whose packed FP32 pairs in the triangle test held k_trace at
@@ -45,6 +46,8 @@ DEVICE_FLAGS.update({"device/rtg_%s.hip" % u: ["-fno-slp-vectorize"] for u in ("
 DEVICE_FLAGS["device/rtg_gbuffer.hip"] = ["-fno-slp-vectorize"]
 # k_shade_pick (rtg_set_light_sampling) is k_shade's body: its unit takes k_shade's flags
 DEVICE_FLAGS["device/rtg_light_pick.hip"] = DEVICE_FLAGS["device/rtg_shade.hip"]
+# ... so is k_shade_grid (rtg_set_light_grid)
+DEVICE_FLAGS["device/rtg_light_grid.hip"] = DEVICE_FLAGS["device/rtg_shade.hip"]
 # ... and so is k_shade_phys (rtg_set_material_model)
 DEVICE_FLAGS["device/rtg_shade_phys.hip"] = DEVICE_FLAGS["device/rtg_shade.hip"]
 # ... and k_shade_mis (rtg_set_path_mis)

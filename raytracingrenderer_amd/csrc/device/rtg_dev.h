@@ -346,6 +346,27 @@ RTG_D int light_pick(const uint4* tab, uint32_t n, uint32_t r0, float d1, float&
     pmf = __uint_as_float(keep ? t.z : t.w);
     return (int)(keep ? k : t.y);
 }
+// rtg_set_light_grid (include/rtg.h has the definition): one such table per cell of a grid over the
+// scene's bounds, table[c * n_lights + k]; the cell of a shading point is three multiplies, clamps and
+// conversions on values the lane already holds, so the pick stays one dependent 16-byte load. IEEE
+// float32 in the order written (no contraction); a NaN coordinate gives index 0 (fmaxf returns the other
+// operand). k_shade_grid's pick sites and k_probe_light_grid share this body.
+struct LightGrid {
+    const uint4* table;  // [cells * n_lights]
+    uint32_t dims[3];
+    float lo[3], scale[3];
+};
+RTG_D uint32_t light_grid_axis(float x, float lo, float scale, uint32_t dim) {
+    const float u = (x - lo) * scale;
+    return (uint32_t)(int)fminf(fmaxf(u, 0.0f), (float)(dim - 1u));
+}
+template <class G>  // (LightGrid, in whatever address space the caller holds it)
+RTG_D uint32_t light_grid_cell(const G& g, v3 x) {
+    const uint32_t ix = light_grid_axis(x.x, g.lo[0], g.scale[0], g.dims[0]);
+    const uint32_t iy = light_grid_axis(x.y, g.lo[1], g.scale[1], g.dims[1]);
+    const uint32_t iz = light_grid_axis(x.z, g.lo[2], g.scale[2], g.dims[2]);
+    return (iz * g.dims[1] + iy) * g.dims[0] + ix;
+}
 
 // ------------------------------------------------------------------ camera sampling
 // rtg_set_camera_sampling (include/rtg.h): where sample `sample` of pixel `pixel` crosses the film

@@ -428,6 +428,8 @@ struct SceneBufs {
 struct ModeTables {
     DevBuf<uint4> env;            // rtg_set_env_sampling: one entry per cell of the environment map
     DevBuf<uint4> light;          // rtg_set_light_sampling: one entry per light
+    DevBuf<uint4> grid;           // rtg_set_light_grid: one such table per cell
+    DevBuf<LightGrid> grid_rec;   // ... and the LightGrid record k_shade_grid reads (table, dims, lo, scale)
     DevBuf<PhysMat> phys;         // rtg_set_material_model: the unique parameter records
     DevBuf<unsigned> phys_index;  // ... and one index into them per triangle
     DevBuf<uint2> mis_index;      // rtg_set_path_mis: MisArgs::index
@@ -517,6 +519,17 @@ struct rtg_handle {
     std::vector<uint32_t> light_entries;  // the table's host copy (rtg_light_table)
     std::vector<double> light_weights;    // the weights it was built from (rtg_light_weights)
     double light_build_ms = 0.0;
+    // rtg_set_light_grid (rtg_light_grid.hip): one alias table per cell of a grid over the root box, built
+    // when the setting is on and RTG_LIGHTS_POWER has a table, rebuilt when cells or uniform_share changes,
+    // kept until rtg_destroy
+    rtg_light_grid light_grid{0};
+    bool grid_built = false;            // mt.grid holds grid_built_cells / grid_built_share
+    uint32_t grid_built_cells = 0;
+    float grid_built_share = 0.0f;
+    uint32_t grid_dims[3] = {0, 0, 0};
+    float grid_lo[3] = {0, 0, 0}, grid_scale[3] = {0, 0, 0};
+    std::vector<uint32_t> grid_entries;   // the tables' host copy (rtg_light_grid_table)
+    double grid_build_ms = 0.0;
     // rtg_set_material_model (rtg_shade_phys.hip): the parameter records of rtg_set_material_params, and
     // the device table (unique records + one index per triangle) built from them by the first
     // RTG_MATERIALS_PHYSICAL setting, rebuilt when the parameters change, kept until rtg_destroy
@@ -678,6 +691,11 @@ static inline EnvTable env_table_set(const rtg_handle* h) {
 }
 // RTG_ERR_ARG (with "who: ..." as the message) for a setting outside include/rtg.h's ranges
 int light_sampling_check(const char* who, const rtg_light_sampling* p);
+// rtg_light_grid.hip: builds the grid's tables when the handle's two settings ask for them and they are
+// not the ones it holds (called by both setters once the device is idle)
+int light_grid_sync(rtg_handle* h);
+// ... and RTG_ERR_ARG (with "who: ..." as the message) for a setting outside include/rtg.h's ranges
+int light_grid_check(const char* who, const rtg_handle* h, const rtg_light_grid* p);
 // rtg_shade_mis.hip: k_shade_mis's per-triangle table from the light list and the handle's parameter
 // index (a no-op before the first RTG_PATH_MIS_POWER setting); the caller has waited for the device
 int mis_sync_tables(rtg_handle* h);
@@ -689,18 +707,20 @@ int material_params_check(const char* who, const rtg_material_params* params, ui
 //   Plain     k_shade<alt, tab>                rtg_shade.hip       today's launches
 //   Env       k_shade_env<alt, tab>            rtg_shade.hip       RTG_ENV_LUMINANCE with a table
 //   Pick      k_shade_pick<alt, tab, env>      rtg_light_pick.hip  RTG_LIGHTS_POWER with a table
+//   Grid      k_shade_grid<alt, tab, env>      rtg_light_grid.hip  ... and rtg_set_light_grid's tables
 //   Phys      k_shade_phys<alt, tab>           rtg_shade_phys.hip  RTG_MATERIALS_PHYSICAL with such a record
 //   Mis       k_shade_mis<tab>                 rtg_shade_mis.hip   RTG_PATH_MIS_POWER under PATH
 //   Trans     k_shade_trans<alt, tab>          rtg_shade_trans.hip ... with a rough dielectric record
 //   TransMis  k_shade_trans_mis<tab>           rtg_shade_trans.hip ... and RTG_PATH_MIS_POWER under PATH
 // From Phys on, the environment table and the light pick are run-time arguments (a null table: uniform).
-enum class ShadeFamily { Plain, Env, Pick, Phys, Mis, Trans, TransMis };
+enum class ShadeFamily { Plain, Env, Pick, Grid, Phys, Mis, Trans, TransMis };
 struct ShadeMode {
     ShadeFamily family;
     bool alt;       // every per-pixel estimator (a.mode) instead of pathTrace alone
     bool tab;       // the material, light and parameter records fit the kernel's LDS tables
     EnvTable env;   // a null table: uniform sampling of the environment light
     LightPick pick; // a null table: the uniform pick
+    const LightGrid* grid;  // Grid alone: the grid's record on the device (the per-cell tables in pick's place)
     PhysArgs phys;  // a null table: the reference model (Mis: reference-kind records for every index)
     MisArgs mis;
 };
@@ -710,6 +730,8 @@ ShadeMode shade_mode_of(const rtg_handle* h);
 int launch_shade(const ShadeMode& m, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
                  const PathBufs& p, int b);
 int launch_shade_pick(const ShadeMode& m, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
+                      const PathBufs& p, int b);
+int launch_shade_grid(const ShadeMode& m, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
                       const PathBufs& p, int b);
 int launch_shade_phys(const ShadeMode& m, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
                       const PathBufs& p, int b);

@@ -156,7 +156,7 @@ int rtg_set_light_sampling(rtg_handle* h, const rtg_light_sampling* p) {
     if (p->mode == RTG_LIGHTS_POWER && (!h->light_built || h->light_built_share != p->uniform_share))
         if (int rc = build_light_table(h, p->uniform_share)) return rc;
     h->light_sampling = *p;
-    return RTG_OK;
+    return light_grid_sync(h);  // rtg_set_light_grid's tables follow the mode and uniform_share
 }
 
 int rtg_get_light_sampling(rtg_handle* h, rtg_light_sampling* p) {

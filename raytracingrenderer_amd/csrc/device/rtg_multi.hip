@@ -504,6 +504,16 @@ int rtg_group_set_light_sampling(rtg_group* g, const rtg_light_sampling* p) {
                               [](rtg_handle* h, const rtg_light_sampling& v) { return rtg_set_light_sampling(h, &v); });
 }
 
+int rtg_group_set_light_grid(rtg_group* g, const rtg_light_grid* p) {
+    if (!g) { g_err = "rtg_group_set_light_grid: null group"; return RTG_ERR_ARG; }
+    // checked once for all ranks (they hold the same light list), so an argument error leaves every rank's
+    // setting as it was; every rank builds its own tables, the same bits from the same records
+    for (rtg_handle* h : g->h)
+        if (int rc = light_grid_check("rtg_group_set_light_grid", h, p)) return rc;
+    return set_all_or_restore(g, *p, rtg_get_light_grid,
+                              [](rtg_handle* h, const rtg_light_grid& v) { return rtg_set_light_grid(h, &v); });
+}
+
 int rtg_group_set_material_params(rtg_group* g, const rtg_material_params* params, uint32_t n) {
     if (!g) { g_err = "rtg_group_set_material_params: null group"; return RTG_ERR_ARG; }
     // checked once for all ranks, so an argument error leaves every rank's records as they were

@@ -362,11 +362,13 @@ ShadeMode shade_mode_of(const rtg_handle* h) {
     if (physical && h->trans_any) m.family = mis ? ShadeFamily::TransMis : ShadeFamily::Trans;
     else if (mis) m.family = ShadeFamily::Mis;
     else if (m.phys.table) m.family = ShadeFamily::Phys;
+    else if (m.pick.table && h->light_grid.cells && h->mt.grid.p && h->mt.grid_rec.p) m.family = ShadeFamily::Grid;
     else if (m.pick.table) m.family = ShadeFamily::Pick;
     else m.family = m.env.table ? ShadeFamily::Env : ShadeFamily::Plain;
     // k_shade_mis under the reference model, or in a scene without a physical record: reference-kind
     // records for every index
     if (m.family == ShadeFamily::Mis && !m.phys.table) m.phys = PhysArgs{h->mt.mis_ref.p, nullptr, h->n_mis_ref};
+    if (m.family == ShadeFamily::Grid) m.grid = h->mt.grid_rec.p;
     m.tab = h->sv.n_mats <= RTG_LDS_MATS && h->sv.n_lights <= RTG_LDS_LIGHTS && m.phys.n <= RTG_LDS_PHYS;
     return m;
 }
@@ -375,6 +377,7 @@ static int launch_shade_bounce(const ShadeMode& m, unsigned grid, hipStream_t st
                                const PathBufs& p, int b) {
     switch (m.family) {
     case ShadeFamily::Pick: return launch_shade_pick(m, grid, st, s, a, p, b);
+    case ShadeFamily::Grid: return launch_shade_grid(m, grid, st, s, a, p, b);
     case ShadeFamily::Phys: return launch_shade_phys(m, grid, st, s, a, p, b);
     case ShadeFamily::Mis: return launch_shade_mis(m, grid, st, s, a, p, b);
     case ShadeFamily::Trans:

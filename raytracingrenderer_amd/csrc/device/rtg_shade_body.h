@@ -30,6 +30,11 @@
 // the rough dielectric's reflection and transmission lobes: |dot(wi, sN)| in NEE's geometry term, the
 // model's evaluate and PDF on the whole sphere, its sample at the bounce. Every statement of it stands
 // inside #ifdef RTG_SHADE_TRANS.
+// RTG_SHADE_GRID defined (k_shade_grid, rtg_light_grid.hip; the including kernel also sets lgr, a reference
+// to the LightGrid record in the constant address space, PICK = true and a null lpk): the table of a pick is
+// the one of the grid cell that holds the shading point x (rtg_set_light_grid), read from global memory, at
+// the two pick sites of DIRECT_MIS and computeDirect; no copy of a table goes to LDS. Every statement of it stands inside #ifdef RTG_SHADE_GRID
+// (DESIGN.md 8l).
     __shared__ unsigned s_cnt[2][RTG_TB / 64];
     __shared__ unsigned s_base[2];
     __shared__ float4 s_sho[RTG_TB], s_shd[RTG_TB];  // NEE ray staged until its queue position is known
@@ -38,6 +43,8 @@
 #ifdef RTG_SHADE_PHYS
     __shared__ uint4 s_pk[TAB ? RTG_LDS_LIGHTS : 1];
     __shared__ PhysMat s_pm[TAB ? RTG_LDS_PHYS : 1];  // the material parameter table (three pieces per record)
+#elif defined(RTG_SHADE_GRID)
+    __shared__ uint4 s_pk[1];  // (the grid's tables stay in global memory)
 #else
     __shared__ uint4 s_pk[(PICK && TAB) ? RTG_LDS_LIGHTS : 1];  // the light-pick table (one entry per light)
 #endif
@@ -76,8 +83,10 @@
         if ((int)threadIdx.x < 5 * s.n_lights)
             __builtin_amdgcn_global_load_lds((gptr_t)(reinterpret_cast<const float4*>(s.lights) + threadIdx.x),
                                              (lptr_t)(reinterpret_cast<float4*>(s_lt) + w0), 16, 0, 0);
+#ifndef RTG_SHADE_GRID
         if (PICK && (int)threadIdx.x < s.n_lights)  // n_lights <= RTG_LDS_LIGHTS < 64: wave 0's lanes
             __builtin_amdgcn_global_load_lds((gptr_t)(lpk.table + threadIdx.x), (lptr_t)(s_pk + w0), 16, 0, 0);
+#endif
 #ifdef RTG_SHADE_PHYS
         if ((int)threadIdx.x < 3 * pm.n)  // pm.n <= RTG_LDS_PHYS: at most 192 pieces
             __builtin_amdgcn_global_load_lds((gptr_t)(reinterpret_cast<const float4*>(pm.table) + threadIdx.x),
@@ -236,7 +245,11 @@
                         if (PICK) {  // RTG_LIGHTS_POWER: r0, d1, always both
                             const uint32_t r0 = pcg_step(st, inc);
                             const float d1 = pcg_next(st, inc);
+#ifdef RTG_SHADE_GRID
+                            li = light_pick(lgr.table + light_grid_cell(lgr, x) * (uint32_t)nl, (uint32_t)nl, r0, d1, pmf);
+#else
                             li = light_pick(TAB ? s_pk : lpk.table, (uint32_t)nl, r0, d1, pmf);
+#endif
                         } else {
                             pmf = s.pmf;  // 1.f / (float)nl
                             li = (int)((float)nl * pcg_next(st, inc));
@@ -349,7 +362,11 @@
                         if (PICK) {  // RTG_LIGHTS_POWER: r0, d1, always both
                             const uint32_t r0 = pcg_step(st, inc);
                             const float d1 = pcg_next(st, inc);
+#ifdef RTG_SHADE_GRID
+                            li = light_pick(lgr.table + light_grid_cell(lgr, x) * (uint32_t)nl, (uint32_t)nl, r0, d1, pmf);
+#else
                             li = light_pick(TAB ? s_pk : lpk.table, (uint32_t)nl, r0, d1, pmf);
+#endif
                         } else {
                             li = (int)((float)nl * pcg_next(st, inc));
                             li = (nl - 1) < li ? (nl - 1) : li;  // (std::min)(a, b)

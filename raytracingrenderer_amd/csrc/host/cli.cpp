@@ -30,7 +30,9 @@
 // Light selection for NEE (rtg_set_light_sampling): -lightSampling uniform|power (uniform: the
 // reference's Scene::sampleLight; power: lights picked by emitted power through an alias table) and
 // -lightUniformShare x (the share of the uniform pick mixed in, default 0.125), for one device and for
-// -gpus / -devices alike.
+// -gpus / -devices alike. -lightGrid N (default 0, off; with -lightSampling power): the pick comes from
+// the alias table of the grid cell that holds the shading point, N cells on the scene's longest axis
+// (rtg_set_light_grid).
 // Material model (rtg_set_material_model): -materials reference|physical (reference: conductor, plastic
 // and Oren-Nayar materials shade as the reference's Lambertian stubs; physical: GGX conductor, coated
 // plastic and Oren-Nayar from the scene's own roughness, eta, k, IORs and alpha), for one device and for
@@ -132,6 +134,11 @@ int main(int argc, char** argv) {
     if (lsn != "uniform" && lsn != "power") return die("-lightSampling", "one of uniform, power");
     lsm.mode = lsn == "power" ? RTG_LIGHTS_POWER : RTG_LIGHTS_UNIFORM;
     lsm.uniform_share = std::stof(get("-lightUniformShare", "0.125"));
+    rtg_light_grid lgr{};
+    rtg_light_grid_defaults(&lgr);
+    const int lgn = std::stoi(get("-lightGrid", "0"));
+    if (lgn < 0) return die("-lightGrid", "0 (off) or the number of cells on the longest axis");
+    lgr.cells = (uint32_t)lgn;
     const std::string mtl = get("-materials", "reference");
     if (mtl != "reference" && mtl != "physical") return die("-materials", "one of reference, physical");
     const bool physical = mtl == "physical";
@@ -178,6 +185,7 @@ int main(int argc, char** argv) {
         if (rtg_set_camera_sampling(rt, &cs) != 0) return die("rtg_set_camera_sampling", rtg_last_error());
         if (rtg_set_env_sampling(rt, env_mode) != 0) return die("rtg_set_env_sampling", rtg_last_error());
         if (rtg_set_light_sampling(rt, &lsm) != 0) return die("rtg_set_light_sampling", rtg_last_error());
+        if (rtg_set_light_grid(rt, &lgr) != 0) return die("rtg_set_light_grid", rtg_last_error());
         if (physical && (rtg_set_material_params(rt, params, n_params) != 0 ||
                          rtg_set_material_model(rt, RTG_MATERIALS_PHYSICAL) != 0))
             return die("rtg_set_material_model", rtg_last_error());
@@ -190,6 +198,7 @@ int main(int argc, char** argv) {
         if (rtg_group_set_camera_sampling(grp, &cs) != 0) return die("rtg_group_set_camera_sampling", rtg_last_error());
         if (rtg_group_set_env_sampling(grp, env_mode) != 0) return die("rtg_group_set_env_sampling", rtg_last_error());
         if (rtg_group_set_light_sampling(grp, &lsm) != 0) return die("rtg_group_set_light_sampling", rtg_last_error());
+        if (rtg_group_set_light_grid(grp, &lgr) != 0) return die("rtg_group_set_light_grid", rtg_last_error());
         if (physical && (rtg_group_set_material_params(grp, params, n_params) != 0 ||
                          rtg_group_set_material_model(grp, RTG_MATERIALS_PHYSICAL) != 0))
             return die("rtg_group_set_material_model", rtg_last_error());

@@ -713,6 +713,58 @@ class RayTracer:
         return {"prob": e[:, 0].copy(), "alias": u[:, 1].copy(), "pmf_self": e[:, 2].copy(),
                 "pmf_alias": e[:, 3].copy(), "entries": u.copy(), "weights": wt, "build_ms": ms.value}
 
+    def set_light_grid(self, cells=8):
+        """Per-shading-point light selection (rtg_set_light_grid): with set_light_sampling("power") active,
+        the light of an NEE sample is picked from the alias table of the grid cell that holds the shading
+        point, each light weighted by its power over its squared distance to the cell (0 where it faces
+        away), mixed with uniform_share of the uniform pick. cells (1..64) is the number of cells on the
+        longest axis of the scene's bounds; 0 turns it off (the default state). 8 is a stated choice, not
+        an optimum (DESIGN.md 8l has the measurements). The same expectation as the other modes, with less
+        noise where many similar lights are spread over the scene. The setting is kept whatever the light
+        mode; frames that run the physical material model's, the path-MIS or the transmission kernels
+        keep the power pick."""
+        p = N.rtg_light_grid(int(cells))
+        _check(self._lib.rtg_set_light_grid(self._h, C.byref(p)), self._lib.rtg_last_error)
+
+    def light_grid(self):
+        """The current setting and the active grid: {"cells", "active", "dims" (3,), "lo" (3,), "scale"
+        (3,), "n_entries", "build_ms"} (dims, lo, scale as the kernel uses them; zeros when no grid is
+        active)."""
+        p = N.rtg_light_grid()
+        _check(self._lib.rtg_get_light_grid(self._h, C.byref(p)), self._lib.rtg_last_error)
+        dims, lo, sc = np.zeros(3, np.uint32), np.zeros(3, np.float32), np.zeros(3, np.float32)
+        ne, ms = C.c_uint64(), C.c_double()
+        _check(self._lib.rtg_light_grid_info(self._h, N.ptr(dims, C.c_uint32), N.ptr(lo, C.c_float),
+                                             N.ptr(sc, C.c_float), C.byref(ne), C.byref(ms)), self._lib.rtg_last_error)
+        return {"cells": int(p.cells), "active": ne.value != 0, "dims": dims, "lo": lo, "scale": sc,
+                "n_entries": int(ne.value), "build_ms": ms.value}
+
+    def light_grid_table(self):
+        """The active grid's tables (rtg_light_grid_table): (cells, n_lights, 4) uint32, the words as the
+        kernel loads them, cell c = (i_z * dims_y + i_y) * dims_x + i_x; None when no grid is active."""
+        g = self.light_grid()
+        if not g["active"]:
+            return None
+        e = np.zeros((g["n_entries"], 4), np.float32)
+        _check(self._lib.rtg_light_grid_table(self._h, N.ptr(e, C.c_float)), self._lib.rtg_last_error)
+        return e.view(np.uint32).reshape(-1, len(self.scene.lights), 4).copy()
+
+    def light_grid_probe(self, points, r0, d1):
+        """The shading kernel's own cell and pick (rtg_probe_light_grid) for points (n, 3) float32 and
+        scripted draws r0 (n,) uint32, d1 (n,) float32 against the active grid: (cell (n,) int32, li (n,)
+        int32, pmf (n,) float32)."""
+        x = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        r = np.ascontiguousarray(r0, np.uint32).reshape(-1)
+        d = np.ascontiguousarray(d1, np.float32).reshape(-1)
+        if len(r) != len(d) or len(r) != len(x):
+            raise ValueError("light_grid_probe: points, r0 and d1 must have one length")
+        cell, li = np.zeros(len(r), np.int32), np.zeros(len(r), np.int32)
+        pmf = np.zeros(len(r), np.float32)
+        _check(self._lib.rtg_probe_light_grid(self._h, N.ptr(x, C.c_float), N.ptr(r, C.c_uint32), N.ptr(d, C.c_float),
+                                              len(r), N.ptr(cell, C.c_int32), N.ptr(li, C.c_int32),
+                                              N.ptr(pmf, C.c_float)), self._lib.rtg_last_error)
+        return cell, li, pmf
+
     def set_material_model(self, mode="reference", transmission=False):
         """How conductor, plastic and Oren-Nayar materials shade (rtg_set_material_model). "reference"
         (default): as RTBase's stubs do, a cosine-sampled Lambertian, the reference's films bit for bit.
@@ -1019,6 +1071,11 @@ class RayTracerGroup:
         """RayTracer.set_light_sampling on every rank (rtg_group_set_light_sampling)."""
         p = _light_sampling(mode, uniform_share)
         _check(self._lib.rtg_group_set_light_sampling(self._g, C.byref(p)), self._lib.rtg_last_error)
+
+    def set_light_grid(self, cells=8):
+        """RayTracer.set_light_grid on every rank (rtg_group_set_light_grid)."""
+        p = N.rtg_light_grid(int(cells))
+        _check(self._lib.rtg_group_set_light_grid(self._g, C.byref(p)), self._lib.rtg_last_error)
 
     def set_path_mis(self, mode="off"):
         """RayTracer.set_path_mis on every rank (rtg_group_set_path_mis)."""

@@ -746,6 +746,65 @@ int  rtg_probe_env_pdf(rtg_handle* h, const float* dirs /* n*3 */, uint32_t n, f
 /* The host copy of the triangle -> light map. Before the first RTG_PATH_MIS_POWER setting: RTG_ERR_ARG. */
 int  rtg_light_of_triangle(rtg_handle* h, int32_t* out /* n_triangles */);
 
+/* ---- the sampler: where a path's and a camera sample's random numbers come from (DESIGN.md §8m;
+ * rtg_sampler.h). RTG_SAMPLER_PCG, the default, untouched: one PCG32 stream per (pixel, sample), white
+ * noise. RTG_SAMPLER_SOBOL: Burley's hash-based Owen-scrambled Sobol sequence (JCGT 2020, "Practical
+ * Hash-Based Owen Scrambling"), padded 4-D: each consecutive group of four draws of a path is one point of
+ * a 4-D Sobol sequence indexed by the pixel's sample number, shuffled and scrambled with a hash seed of the
+ * group's own, so the samples of a pixel are stratified against each other in every group, whatever the
+ * chunking, tiling, queuing or rank split. It changes no estimator, only where the numbers come from: a
+ * film stays a deterministic function of (pixel, sample, seed). Definition; all arithmetic is uint32 with
+ * wrap-around, brev is a 32-bit bit reversal:
+ *   mix32(x):   x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *   lk(x, s):   x += s; x ^= x * 0x6c50b47c; x ^= x * 0xb82f1e52; x ^= x * 0xc7afe638; x ^= x * 0x8d22f6e6
+ *   owen(x, s): brev(lk(brev(x), s))
+ *   key(pixel, seed, stream) = mix32(pixel ^ mix32((uint32)seed ^ mix32((uint32)(seed >> 32) ^ stream)))
+ *        stream: 0 for the path, 0x9E3779B9 for the camera sample (the PCG mode keys its camera stream
+ *        apart too)
+ *   draw n of (pixel, sample):   g = n >> 2,  c = n & 3
+ *        gs  = mix32(key ^ (g * 0x9E3779B9))
+ *        idx = owen(sample, gs) & 0xFFFF            (the sample number enters by its low 16 bits)
+ *        X   = owen(sobol_c(idx), mix32(gs + (c + 1) * 0x85EBCA6B))
+ *        sobol_c(idx) = XOR over the set bits b < 16 of idx of D_c[b];   D_0[b] = 0x80000000 >> b
+ *   raw 32-bit draw = X  (where the body uses pcg_step's output: the alias picks' r0)
+ *   float draw      = (float)(X >> 8) * 2^-24       (exactly pcg_next's conversion)
+ * D_1, D_2, D_3 are the Joe-Kuo direction words of dimensions 2, 3 and 4 (polynomial degree / a / m =
+ * 1/0/(1), 2/1/(1,3), 3/1/(1,3,1); the standard recurrence with v_i = m_i << (31 - i)); the first 16 of each:
+ *   D_1 = 80000000 c0000000 a0000000 f0000000 88000000 cc000000 aa000000 ff000000
+ *         80800000 c0c00000 a0a00000 f0f00000 88880000 cccc0000 aaaa0000 ffff0000
+ *   D_2 = 80000000 c0000000 60000000 90000000 e8000000 5c000000 8e000000 c5000000
+ *         68800000 9cc00000 ee600000 55900000 80680000 c09c0000 60ee0000 90550000
+ *   D_3 = 80000000 c0000000 20000000 50000000 f8000000 74000000 a2000000 93000000
+ *         d8800000 25400000 59e00000 e6d00000 78080000 b40c0000 82020000 c3050000
+ * Check values: mix32(5) = 0x5c45d53e; with key = mix32(5) and g = 0, sample 0 draws f71b8747 85be176b
+ * 3945034a 6243e999 (components 0..3) and sample 65535 draws 73c1d462 9ef285ce 288746e5 5010ac28.
+ * The draw counter n is 0 at the camera bounce and advances by one per draw, raw or float, at exactly the
+ * sites where the PCG body draws, in the same order. It travels in the low 32 bits of the path's rng
+ * payload word (the high 32 bits are the implementation's). When a bounce b >= 1 loads it, it is first
+ * rounded up to a multiple of 4, so every bounce opens on a fresh 4-D point and the light sample's
+ * (r0, d1, r1, r2) is one point. The camera sample (rtg_set_camera_sampling) takes draws 0..3 of the camera
+ * stream: u0..u3 are one 4-D point, film x, film y and the lens.
+ * Scope: rtg_render, rtg_render_async, rtg_render_adaptive and the group calls, under RTG_INTEGRATOR_PATH,
+ * _DIRECT and _DIRECT_MIS, with either environment mode, the uniform and the power light pick, and both
+ * camera modes (kernels of their own: k_sobol_shade, k_sobol_shade_env, k_sobol_shade_pick,
+ * k_sobol_generate_sampled; the default's are not touched). A frame that runs the light grid's, the
+ * physical material model's, rtg_set_path_mis's or the rough dielectric's kernels keeps the PCG streams,
+ * camera samples included, and so do rtg_render_light and rtg_render_instant_radiosity; _ALBEDO, _NORMALS,
+ * rtg_gbuffer and the denoiser's guides draw nothing. rtg_sampler_active reports what the next rtg_render
+ * would run, so the fallback is not silent; rtg_probe_camera_samples follows it. The setter first issues
+ * and waits for queued frames; an unknown value is RTG_ERR_ARG and leaves the previous setting in place. */
+#define RTG_SAMPLER_PCG   0
+#define RTG_SAMPLER_SOBOL 1
+int  rtg_sampler_check(int sampler);  /* rtg_set_sampler's argument check alone (no device) */
+int  rtg_set_sampler(rtg_handle* h, int sampler);
+int  rtg_get_sampler(rtg_handle* h, int* sampler);
+int  rtg_sampler_active(rtg_handle* h, int* sampler);
+/* The kernels' own draw function on the current device (no handle): out_raw[i * n_draws + k] is raw draw
+ * first_draw + k of (pixels[i], samples[i]) under key(pixels[i], seed, stream). No rounding of the counter
+ * between draws. */
+int  rtg_probe_sampler(uint64_t seed, uint32_t stream, const uint32_t* pixels, const uint32_t* samples, uint32_t n,
+                       uint32_t first_draw, uint32_t n_draws, uint32_t* out_raw /* n * n_draws */);
+
 /* ---- a movable camera (rtg_api.hip). The camera enters with rtg_scene_desc at rtg_create;
  * rtg_set_camera replaces both records on a live handle, so a frame loop that moves its camera
  * (Main.cpp:82-111: W/S/A/D/E/Q, then rt.clear()) keeps the handle, its tree and its upload.
@@ -1025,6 +1084,7 @@ int  rtg_group_set_light_grid(rtg_group* g, const rtg_light_grid* p);          /
 int  rtg_group_set_material_params(rtg_group* g, const rtg_material_params* params, uint32_t n);  /* every rank's */
 int  rtg_group_set_material_model(rtg_group* g, int mode);  /* rtg_set_material_model on every rank's handle */
 int  rtg_group_set_path_mis(rtg_group* g, int mode);  /* rtg_set_path_mis on every rank's handle */
+int  rtg_group_set_sampler(rtg_group* g, int sampler);  /* rtg_set_sampler on every rank's handle */
 int  rtg_group_set_camera(rtg_group* g, const rtg_camera* cam, const rtg_camera_proj* proj);  /* every rank's handle */
 int  rtg_group_render(rtg_group* g, uint32_t first_sample, uint32_t n_samples, uint64_t seed);
 int  rtg_group_reduce(rtg_group* g);  /* the films stay per device; the assembled film goes to a separate buffer */

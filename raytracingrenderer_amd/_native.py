@@ -22,6 +22,7 @@ RTG_ENV_MAX_CELLS = 1 << 24
 RTG_LIGHTS_UNIFORM, RTG_LIGHTS_POWER = 0, 1
 RTG_MATERIALS_REFERENCE, RTG_MATERIALS_PHYSICAL = 0, 1
 RTG_PATH_MIS_OFF, RTG_PATH_MIS_POWER = 0, 1
+RTG_SAMPLER_PCG, RTG_SAMPLER_SOBOL = 0, 1
 RTG_MODEL_REFERENCE, RTG_MODEL_CONDUCTOR, RTG_MODEL_PLASTIC, RTG_MODEL_ORENNAYAR = 0, 1, 2, 3
 RTG_MODEL_ROUGH_DIELECTRIC = 5  # (4 is left unassigned)
 RTG_ALPHA_DELTA = 0.01
@@ -234,6 +235,13 @@ RTG_EXPORTS = [
     ("rtg_probe_mis_weight", C.c_int, [f32p, f32p, C.c_uint32, f32p]),
     ("rtg_probe_env_pdf", C.c_int, [C.c_void_p, f32p, C.c_uint32, f32p]),
     ("rtg_light_of_triangle", C.c_int, [C.c_void_p, i32p]),
+    # the sampler: PCG streams or Owen-scrambled Sobol points (rtg_sampler.h)
+    ("rtg_sampler_check", C.c_int, [C.c_int]),
+    ("rtg_set_sampler", C.c_int, [C.c_void_p, C.c_int]),
+    ("rtg_get_sampler", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    ("rtg_sampler_active", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    ("rtg_group_set_sampler", C.c_int, [C.c_void_p, C.c_int]),
+    ("rtg_probe_sampler", C.c_int, [C.c_uint64, C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, u32p]),
     # a movable camera (rtg_api.hip)
     ("rtg_set_camera", C.c_int, [C.c_void_p, C.POINTER(rtg_camera), C.POINTER(rtg_camera_proj)]),
     ("rtg_get_camera", C.c_int, [C.c_void_p, C.POINTER(rtg_camera), C.POINTER(rtg_camera_proj)]),
@@ -321,3 +329,22 @@ def rtg():
 
 def ptr(arr, ctype):
     return arr.ctypes.data_as(C.POINTER(ctype))
+
+
+def probe_sampler(seed, pixels, samples, n_draws, first_draw=0, stream=0):
+    """The Sobol sampler's raw draws as the kernels compute them (rtg_probe_sampler, test surface) on the
+    current device: (n, n_draws) uint32, draws first_draw.. of each (pixels[i], samples[i]) under the
+    key of (pixel, seed, stream); no rounding of the counter between draws."""
+    import numpy as np
+    px = np.ascontiguousarray(pixels, np.uint32).ravel()
+    sm = np.ascontiguousarray(samples, np.uint32).ravel()
+    if len(px) != len(sm):
+        raise ValueError("pixels and samples must have the same length")
+    out = np.zeros((len(px), int(n_draws)), np.uint32)
+    lib = rtg()
+    rc = lib.rtg_probe_sampler(int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), ptr(px, C.c_uint32), ptr(sm, C.c_uint32),
+                               len(px), int(first_draw), int(n_draws), ptr(out, C.c_uint32))
+    if rc != 0:
+        from .renderer import NativeError  # (renderer imports this module)
+        raise NativeError("%s (code %d)" % (lib.rtg_last_error().decode(errors="replace"), rc))
+    return out

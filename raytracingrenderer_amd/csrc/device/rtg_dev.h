@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "../../../include/rtg_math.h"
+#include "rtg_sampler.h"
 
 #define RTG_D __device__ __forceinline__
 #define RTG_FLT_MAX 3.40282347e+38f
@@ -374,7 +375,8 @@ RTG_D uint32_t light_grid_cell(const G& g, v3 x) {
 // seed xor 0x9E3779B97F4A7C15, so the path's stream (k_shade) draws what it draws without it. Four
 // draws in order, always all four: u0 (film x), u1 (film y), u2, u3 (lens). filter: 0 none, 1 box,
 // 2 tent (RTG_FILTER_*). IEEE float32 in the order written (no contraction); a zero offset leaves
-// k_generate's pixel-centre ray bit for bit.
+// k_generate's pixel-centre ray bit for bit. SOBOL (rtg_set_sampler, RTG_SAMPLER_SOBOL): u0..u3 are draws
+// 0..3 of rtg_sampler.h's camera stream, one 4-D point; the default is the PCG stream.
 struct CamSampling {
     int filter;
     float filter_radius, lens_radius, focal_distance;
@@ -408,16 +410,27 @@ RTG_D v3 camera_dir(const DevCamera& cam, float px, float py) {
 //   ft = f / fabsf(dot(d, zc))            P  = add(o, muls(d, ft))           (the point in focus)
 //   rr = R * sqrtf(u2)                    (s, c) = rtm_sincosf(6.2831855f * u3)
 //   o' = add(add(o, muls(xc, rr * c)), muls(yc, rr * s))                     d' = normalize(sub(P, o'))
+template <bool SOBOL = false>
 RTG_D void camera_sample(const DevCamera& cam, unsigned pixel, unsigned sample, uint64_t seed, const CamSampling& cs,
                          float& fx, float& fy, v3& o, v3& d) {
     const unsigned W = (unsigned)cam.width;
     const unsigned x = pixel % W, y = pixel / W;
-    const uint64_t inc = pcg_inc(pixel, sample);
-    uint64_t st = pcg_seed(seed ^ 0x9E3779B97F4A7C15ull, inc);
-    const float u0 = pcg_next(st, inc);
-    const float u1 = pcg_next(st, inc);
-    const float u2 = pcg_next(st, inc);
-    const float u3 = pcg_next(st, inc);
+    float u0, u1, u2, u3;
+    if (SOBOL) {
+        const uint64_t inc = (uint64_t)sobol_key(pixel, seed, RTG_SOBOL_CAMERA_STREAM) | ((uint64_t)sample << 32);
+        uint64_t st = 0;
+        u0 = sobol_next(st, inc);
+        u1 = sobol_next(st, inc);
+        u2 = sobol_next(st, inc);
+        u3 = sobol_next(st, inc);
+    } else {
+        const uint64_t inc = pcg_inc(pixel, sample);
+        uint64_t st = pcg_seed(seed ^ 0x9E3779B97F4A7C15ull, inc);
+        u0 = pcg_next(st, inc);
+        u1 = pcg_next(st, inc);
+        u2 = pcg_next(st, inc);
+        u3 = pcg_next(st, inc);
+    }
     fx = ((float)x + 0.5f) + filter_offset(cs.filter, cs.filter_radius, u0);
     fy = ((float)y + 0.5f) + filter_offset(cs.filter, cs.filter_radius, u1);
     o = mk(cam.ox, cam.oy, cam.oz);

@@ -550,6 +550,7 @@ struct rtg_handle {
     std::vector<int32_t> light_tri;            // rtg_scene_desc.lights (upload_scene; host only)
     std::vector<int32_t> light_of;             // [triangle] -> light, the map's host copy (rtg_light_of_triangle)
     int n_mis_ref = 0;
+    int sampler = RTG_SAMPLER_PCG;  // rtg_set_sampler (shade_mode_of decides whether a frame follows it)
     ModeTables mt;  // the device tables of the four settings above
 };
 #define RTG_CNT_PENDING 0xFFFFFFFFu
@@ -713,11 +714,15 @@ int material_params_check(const char* who, const rtg_material_params* params, ui
 //   Trans     k_shade_trans<alt, tab>          rtg_shade_trans.hip ... with a rough dielectric record
 //   TransMis  k_shade_trans_mis<tab>           rtg_shade_trans.hip ... and RTG_PATH_MIS_POWER under PATH
 // From Phys on, the environment table and the light pick are run-time arguments (a null table: uniform).
+// sobol: Plain, Env and Pick under PATH, DIRECT and DIRECT_MIS run their *_sobol kernels (rtg_set_sampler,
+// RTG_SAMPLER_SOBOL), and the frame's camera samples come from k_sobol_generate_sampled; every other
+// family and integrator keeps the PCG streams.
 enum class ShadeFamily { Plain, Env, Pick, Grid, Phys, Mis, Trans, TransMis };
 struct ShadeMode {
     ShadeFamily family;
     bool alt;       // every per-pixel estimator (a.mode) instead of pathTrace alone
     bool tab;       // the material, light and parameter records fit the kernel's LDS tables
+    bool sobol;     // the frame draws from rtg_sampler.h's Sobol points
     EnvTable env;   // a null table: uniform sampling of the environment light
     LightPick pick; // a null table: the uniform pick
     const LightGrid* grid;  // Grid alone: the grid's record on the device (the per-cell tables in pick's place)

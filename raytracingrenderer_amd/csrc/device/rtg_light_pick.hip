@@ -22,7 +22,6 @@ __global__ __launch_bounds__(RTG_TB, ALT ? RTG_SHADE_ENV_ALT_WAVES : RTG_SHADE_W
     constexpr bool PICK = true;
 #include "rtg_shade_body.h"
 }
-
 // rtg_probe_light_pick: light_pick on given draws
 __global__ void k_probe_light_pick(LightPick lpk, unsigned nl, const unsigned* r0, const float* d1, unsigned n, int* li,
                                    float* pmf) {
@@ -33,6 +32,18 @@ __global__ void k_probe_light_pick(LightPick lpk, unsigned nl, const unsigned* r
     pmf[i] = pm;
 }
 
+// k_shade_pick drawing from the Owen-scrambled Sobol sampler (rtg_set_sampler; rtg_sampler.h), as rtg_shade.hip's
+// k_sobol_shade: the waves per SIMD are k_shade_pick's
+#define RTG_SHADE_SOBOL
+template <bool ALT, bool TAB, bool ENVT>
+__global__ __launch_bounds__(RTG_TB, ALT ? RTG_SHADE_ENV_ALT_WAVES : RTG_SHADE_WAVES) void k_sobol_shade_pick(
+    SceneView s, ChunkArgs a, PathBufs p, int b, EnvTable et, LightPick lpk) {
+    constexpr bool ENV = ENVT;
+    constexpr bool PICK = true;
+#include "rtg_shade_body.h"
+}
+#undef RTG_SHADE_SOBOL
+
 int launch_shade_pick(const ShadeMode& m, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
                       const PathBufs& p, int b) {
     const int sel = (m.alt ? 4 : 0) | (m.tab ? 2 : 0) | (m.env.table ? 1 : 0);
@@ -40,7 +51,12 @@ int launch_shade_pick(const ShadeMode& m, unsigned grid, hipStream_t st, const S
         k_shade_pick<false, false, false>, k_shade_pick<false, false, true>, k_shade_pick<false, true, false>,
         k_shade_pick<false, true, true>,   k_shade_pick<true, false, false>, k_shade_pick<true, false, true>,
         k_shade_pick<true, true, false>,   k_shade_pick<true, true, true>};
-    hipLaunchKernelGGL(kern[sel], dim3(grid), dim3(RTG_TB), 0, st, s, a, p, b, m.env, m.pick);
+    void (*const kern_sobol[8])(SceneView, ChunkArgs, PathBufs, int, EnvTable, LightPick) = {
+        k_sobol_shade_pick<false, false, false>, k_sobol_shade_pick<false, false, true>,
+        k_sobol_shade_pick<false, true, false>,  k_sobol_shade_pick<false, true, true>,
+        k_sobol_shade_pick<true, false, false>,  k_sobol_shade_pick<true, false, true>,
+        k_sobol_shade_pick<true, true, false>,   k_sobol_shade_pick<true, true, true>};
+    hipLaunchKernelGGL(m.sobol ? kern_sobol[sel] : kern[sel], dim3(grid), dim3(RTG_TB), 0, st, s, a, p, b, m.env, m.pick);
     LAUNCH_OK("k_shade_pick");
     return RTG_OK;
 }

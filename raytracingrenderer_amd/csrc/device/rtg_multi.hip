@@ -547,6 +547,13 @@ int rtg_group_set_path_mis(rtg_group* g, int mode) {
     return set_all_or_restore(g, mode, rtg_get_path_mis, rtg_set_path_mis);
 }
 
+int rtg_group_set_sampler(rtg_group* g, int sampler) {
+    if (!g) { g_err = "rtg_group_set_sampler: null group"; return RTG_ERR_ARG; }
+    // checked once for all ranks, so an argument error leaves every rank's setting as it was
+    if (int rc = rtg_sampler_check(sampler)) return rc;
+    return set_all_or_restore(g, sampler, rtg_get_sampler, rtg_set_sampler);
+}
+
 int rtg_group_render(rtg_group* g, uint32_t first_sample, uint32_t n_samples, uint64_t seed) {
     if (!g) return RTG_ERR_ARG;
     g->reduced = false;

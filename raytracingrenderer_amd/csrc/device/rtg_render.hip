@@ -84,7 +84,8 @@ __global__ __launch_bounds__(RTG_TB) void k_generate(ChunkArgs a, PathBufs p) {
 // rtg_dev.h) in ray_d[pid], and with a lens its origin in ray_o[pid] (the path id in .w, as later
 // bounces carry it); the rest of the bounce-0 state stays implied, as in k_generate's lean branch.
 // Bounce 0 is then a segmented queue of P rays at identity positions, like every later bounce.
-__global__ __launch_bounds__(RTG_TB) void k_generate_sampled(ChunkArgs a, PathBufs p, CamSampling cs) {
+template <bool SOBOL>
+static __device__ __forceinline__ void generate_sampled(const ChunkArgs& a, const PathBufs& p, const CamSampling& cs) {
     const unsigned pid = blockIdx.x * blockDim.x + threadIdx.x;
     if (pid < 8) {  // the paths as queue segments (positions = path ids), as k_generate
         const unsigned cap = a.seg_tiles * RTG_TB, lo = pid * cap;
@@ -96,19 +97,24 @@ __global__ __launch_bounds__(RTG_TB) void k_generate_sampled(ChunkArgs a, PathBu
     split_pid(a, pid, lp, sl);
     float fx, fy;
     v3 o, d;
-    camera_sample(a.cam, a.pixlist[lp], a.s0 + sl, a.seed, cs, fx, fy, o, d);
+    camera_sample<SOBOL>(a.cam, a.pixlist[lp], a.s0 + sl, a.seed, cs, fx, fy, o, d);
     p.ray_d[pid] = make_float4(d.x, d.y, d.z, 0.0f);
     if (a.cam_mode & RTG_CAM_LENS) p.ray_o[pid] = make_float4(o.x, o.y, o.z, __int_as_float((int)pid));
 }
+__global__ __launch_bounds__(RTG_TB) void k_generate_sampled(ChunkArgs a, PathBufs p, CamSampling cs) {
+    generate_sampled<false>(a, p, cs);
+}
 
 // rtg_probe_camera_samples: camera_sample on given (pixel, sample) pairs
-__global__ void k_probe_camera(DevCamera cam, CamSampling cs, unsigned long long seed, const unsigned* pixels,
-                               const unsigned* samples, unsigned n, float* rays, float* film_xy) {
+template <bool SOBOL>
+static __device__ __forceinline__ void probe_camera(const DevCamera& cam, const CamSampling& cs, unsigned long long seed,
+                                                    const unsigned* pixels, const unsigned* samples, unsigned n,
+                                                    float* rays, float* film_xy) {
     const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float fx, fy;
     v3 o, d;
-    camera_sample(cam, pixels[i], samples[i], seed, cs, fx, fy, o, d);
+    camera_sample<SOBOL>(cam, pixels[i], samples[i], seed, cs, fx, fy, o, d);
     float* r = rays + (size_t)i * 8;
     r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = 0.0f;
     r[4] = d.x; r[5] = d.y; r[6] = d.z; r[7] = 0.0f;
@@ -116,6 +122,10 @@ __global__ void k_probe_camera(DevCamera cam, CamSampling cs, unsigned long long
         film_xy[2 * (size_t)i] = fx;
         film_xy[2 * (size_t)i + 1] = fy;
     }
+}
+__global__ void k_probe_camera(DevCamera cam, CamSampling cs, unsigned long long seed, const unsigned* pixels,
+                               const unsigned* samples, unsigned n, float* rays, float* film_xy) {
+    probe_camera<false>(cam, cs, seed, pixels, samples, n, rays, film_xy);
 }
 
 // ------------------------------------------------------------------ shade: rtg_shade.hip (k_shade, launch_shade)
@@ -222,6 +232,26 @@ __global__ void k_tally(const Counters* ctr, int maxb, unsigned long long* stats
         atomicAdd(&stats[3], sh);
         atomicAdd(&stats[14], (unsigned long long)ctr[0].n_cam);  // camera rays traced (path tracer)
     }
+}
+
+// ------------------------------------------------------------------ the Sobol sampler's kernels (rtg_set_sampler)
+// k_generate_sampled with the four draws from the Sobol sampler's camera stream
+__global__ __launch_bounds__(RTG_TB) void k_sobol_generate_sampled(ChunkArgs a, PathBufs p, CamSampling cs) {
+    generate_sampled<true>(a, p, cs);
+}
+// ... and k_probe_camera
+__global__ void k_sobol_probe_camera(DevCamera cam, CamSampling cs, unsigned long long seed, const unsigned* pixels,
+                                     const unsigned* samples, unsigned n, float* rays, float* film_xy) {
+    probe_camera<true>(cam, cs, seed, pixels, samples, n, rays, film_xy);
+}
+// rtg_probe_sampler: draws first_draw .. first_draw + n_draws - 1 of each (pixel, sample), through the
+// kernels' own sobol_draw (no rounding of the counter between them)
+__global__ void k_probe_sampler(unsigned long long seed, unsigned stream, const unsigned* pixels, const unsigned* samples,
+                                unsigned n, unsigned first_draw, unsigned n_draws, unsigned* out) {
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t key = sobol_key(pixels[i], seed, stream);
+    for (unsigned k = 0; k < n_draws; ++k) out[(size_t)i * n_draws + k] = sobol_draw(key, samples[i], first_draw + k);
 }
 
 // ================================================================== host side
@@ -369,6 +399,9 @@ ShadeMode shade_mode_of(const rtg_handle* h) {
     // records for every index
     if (m.family == ShadeFamily::Mis && !m.phys.table) m.phys = PhysArgs{h->mt.mis_ref.p, nullptr, h->n_mis_ref};
     if (m.family == ShadeFamily::Grid) m.grid = h->mt.grid_rec.p;
+    // rtg_set_sampler: the families with Sobol kernels, under the integrators that draw
+    m.sobol = h->sampler == RTG_SAMPLER_SOBOL && samples_light &&
+              (m.family == ShadeFamily::Plain || m.family == ShadeFamily::Env || m.family == ShadeFamily::Pick);
     m.tab = h->sv.n_mats <= RTG_LDS_MATS && h->sv.n_lights <= RTG_LDS_LIGHTS && m.phys.n <= RTG_LDS_PHYS;
     return m;
 }
@@ -646,8 +679,8 @@ static int issue_chunk(rtg_handle* h, ChunkSlot& sl, const ChunkArgs& a, int max
     {
         RoctxRange r_gen("rtg:generate");
         if (a.cam_mode) {  // rtg_set_camera_sampling: a camera ray per path
-            hipLaunchKernelGGL(k_generate_sampled, dim3((a.P + RTG_TB - 1) / RTG_TB), dim3(RTG_TB), 0, ss, a, pb,
-                               cam_sampling_dev(h));
+            hipLaunchKernelGGL(mode.sobol ? k_sobol_generate_sampled : k_generate_sampled,
+                               dim3((a.P + RTG_TB - 1) / RTG_TB), dim3(RTG_TB), 0, ss, a, pb, cam_sampling_dev(h));
             LAUNCH_OK("k_generate_sampled");
         } else {
             hipLaunchKernelGGL(k_generate, dim3((a.npix + RTG_TB - 1) / RTG_TB), dim3(RTG_TB), 0, ss, a, pb);  // lean: per pixel
@@ -888,10 +921,51 @@ int rtg_probe_camera_samples(rtg_handle* h, const uint32_t* pixels, const uint32
     HIPOK(hipSetDevice(h->device));
     return probe_run({{pixels, (size_t)n * sizeof(unsigned)}, {samples, (size_t)n * sizeof(unsigned)}},
                      {{rays, (size_t)n * 8 * sizeof(float)}, {film_xy, (size_t)n * 2 * sizeof(float)}}, [&](void* const* d) {
-                         hipLaunchKernelGGL(k_probe_camera, dim3((n + 255) / 256), dim3(256), 0, nullptr, h->cam,
+                         hipLaunchKernelGGL(shade_mode_of(h).sobol ? k_sobol_probe_camera : k_probe_camera, dim3((n + 255) / 256), dim3(256), 0, nullptr, h->cam,
                                             cam_sampling_dev(h), (unsigned long long)seed, (const unsigned*)d[0],
                                             (const unsigned*)d[1], (unsigned)n, (float*)d[2], (float*)d[3]);
                      });
+}
+
+int rtg_sampler_check(int sampler) {
+    if (sampler != RTG_SAMPLER_PCG && sampler != RTG_SAMPLER_SOBOL) {
+        g_err = "rtg_set_sampler: unknown sampler";
+        return RTG_ERR_ARG;
+    }
+    return RTG_OK;
+}
+
+int rtg_set_sampler(rtg_handle* h, int sampler) {
+    if (!h) { g_err = "rtg_set_sampler: null handle"; return RTG_ERR_ARG; }
+    if (int rc = rtg_sampler_check(sampler)) return rc;
+    if (int rc = settle(h)) return rc;
+    h->sampler = sampler;
+    return RTG_OK;
+}
+
+int rtg_get_sampler(rtg_handle* h, int* sampler) {
+    if (!h || !sampler) { g_err = "rtg_get_sampler: null argument"; return RTG_ERR_ARG; }
+    *sampler = h->sampler;
+    return RTG_OK;
+}
+
+int rtg_sampler_active(rtg_handle* h, int* sampler) {
+    if (!h || !sampler) { g_err = "rtg_sampler_active: null argument"; return RTG_ERR_ARG; }
+    *sampler = shade_mode_of(h).sobol ? RTG_SAMPLER_SOBOL : RTG_SAMPLER_PCG;
+    return RTG_OK;
+}
+
+int rtg_probe_sampler(uint64_t seed, uint32_t stream, const uint32_t* pixels, const uint32_t* samples, uint32_t n,
+                      uint32_t first_draw, uint32_t n_draws, uint32_t* out_raw) {
+    if (!pixels || !samples || !out_raw) { g_err = "rtg_probe_sampler: null argument"; return RTG_ERR_ARG; }
+    if ((uint64_t)n * n_draws > 0x7fffffffu / 4u) { g_err = "rtg_probe_sampler: too many draws"; return RTG_ERR_ARG; }
+    if (n == 0 || n_draws == 0) return RTG_OK;
+    const size_t bytes = (size_t)n * sizeof(unsigned);
+    return probe_run({{pixels, bytes}, {samples, bytes}}, {{out_raw, bytes * n_draws}}, [&](void* const* d) {
+        hipLaunchKernelGGL(k_probe_sampler, dim3((n + 255) / 256), dim3(256), 0, nullptr, (unsigned long long)seed,
+                           (unsigned)stream, (const unsigned*)d[0], (const unsigned*)d[1], (unsigned)n,
+                           (unsigned)first_draw, (unsigned)n_draws, (unsigned*)d[2]);
+    });
 }
 
 int rtg_render_async(rtg_handle* h, uint32_t first, uint32_t n, uint64_t seed, const uint32_t* tiles,

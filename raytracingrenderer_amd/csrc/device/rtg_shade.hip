@@ -44,22 +44,55 @@ __global__ __launch_bounds__(RTG_TB, ALT ? RTG_SHADE_ENV_ALT_WAVES : RTG_SHADE_W
 #include "rtg_shade_body.h"
 }
 
+// k_shade and k_shade_env drawing from the Owen-scrambled Sobol sampler (rtg_set_sampler, RTG_SAMPLER_SOBOL;
+// rtg_sampler.h): the same body with RTG_SHADE_SOBOL set, in kernels of their own name, so the eight
+// kernels above keep their instructions. The waves per SIMD are their parents', but for k_sobol_shade<true,
+// *>: k_shade<true, *> spills at its 7 waves (46-60 VGPRs) and the draws add to that (57-75), so it takes
+// k_shade_env<true, *>'s RTG_SHADE_ENV_ALT_WAVES, where it holds its state in registers (DESIGN.md §8m has
+// the register table).
+#define RTG_SHADE_SOBOL
+template <bool ALT, bool TAB>
+__global__ __launch_bounds__(RTG_TB, ALT ? RTG_SHADE_ENV_ALT_WAVES : RTG_SHADE_WAVES) void k_sobol_shade(
+    SceneView s, ChunkArgs a, PathBufs p, int b) {
+    constexpr bool ENV = false;
+    const EnvTable et{nullptr, 0u, 0u, 0u};
+    constexpr bool PICK = false;
+    const LightPick lpk{nullptr};
+#include "rtg_shade_body.h"
+}
+template <bool ALT, bool TAB>
+__global__ __launch_bounds__(RTG_TB, ALT ? RTG_SHADE_ENV_ALT_WAVES : RTG_SHADE_WAVES) void k_sobol_shade_env(
+    SceneView s, ChunkArgs a, PathBufs p, int b, EnvTable et) {
+    constexpr bool ENV = true;
+    constexpr bool PICK = false;
+    const LightPick lpk{nullptr};
+#include "rtg_shade_body.h"
+}
+#undef RTG_SHADE_SOBOL
 
 // The launch of one shading bounce (ShadeFamily::Plain and Env): the pathTrace-only kernel or the one
 // holding every per-pixel estimator, with or without the LDS material / light tables.
 int launch_shade(const ShadeMode& m, unsigned grid, hipStream_t st, const SceneView& s, const ChunkArgs& a,
                  const PathBufs& p, int b) {
     const bool alt = m.alt, tab = m.tab;
-    if (m.family == ShadeFamily::Env) {  // RTG_ENV_LUMINANCE with a table (PATH, DIRECT, DIRECT_MIS)
-        auto kenv = alt ? (tab ? k_shade_env<true, true> : k_shade_env<true, false>)
-                        : (tab ? k_shade_env<false, true> : k_shade_env<false, false>);
-        hipLaunchKernelGGL(kenv, dim3(grid), dim3(RTG_TB), 0, st, s, a, p, b, m.env);
-        LAUNCH_OK("k_shade_env");
-        return RTG_OK;
-    }
+    // (the existing kernels are named first, the Sobol variants after them: a unit's kernels are emitted in
+    // the order of their first use, and the existing ones keep their place in it)
+    auto kenv = alt ? (tab ? k_shade_env<true, true> : k_shade_env<true, false>)
+                    : (tab ? k_shade_env<false, true> : k_shade_env<false, false>);
     auto kern = alt ? (tab ? k_shade<true, true> : k_shade<true, false>)
                     : (tab ? k_shade<false, true> : k_shade<false, false>);
+    if (m.sobol) {
+        kenv = alt ? (tab ? k_sobol_shade_env<true, true> : k_sobol_shade_env<true, false>)
+                   : (tab ? k_sobol_shade_env<false, true> : k_sobol_shade_env<false, false>);
+        kern = alt ? (tab ? k_sobol_shade<true, true> : k_sobol_shade<true, false>)
+                   : (tab ? k_sobol_shade<false, true> : k_sobol_shade<false, false>);
+    }
+    if (m.family == ShadeFamily::Env) {  // RTG_ENV_LUMINANCE with a table (PATH, DIRECT, DIRECT_MIS)
+        hipLaunchKernelGGL(kenv, dim3(grid), dim3(RTG_TB), 0, st, s, a, p, b, m.env);
+        LAUNCH_OK((m.sobol ? "k_sobol_shade_env" : "k_shade_env"));
+        return RTG_OK;
+    }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(RTG_TB), 0, st, s, a, p, b);
-    LAUNCH_OK("k_shade");
+    LAUNCH_OK((m.sobol ? "k_sobol_shade" : "k_shade"));
     return RTG_OK;
 }

@@ -35,6 +35,26 @@
 // the one of the grid cell that holds the shading point x (rtg_set_light_grid), read from global memory, at
 // the two pick sites of DIRECT_MIS and computeDirect; no copy of a table goes to LDS. Every statement of it stands inside #ifdef RTG_SHADE_GRID
 // (DESIGN.md 8l).
+// RTG_SHADE_SOBOL defined (k_sobol_shade, k_sobol_shade_env, k_sobol_shade_pick): every draw of the path
+// comes from rtg_sampler.h's Owen-scrambled Sobol points in the PCG stream's place (rtg_set_sampler): st
+// is the draw counter, rounded up to a multiple of four when a bounce loads it, and inc holds the key and
+// the sample number. The draw sites and their order are the PCG body's: they go through the RTG_RNG_*
+// names below, which without the macro are the PCG calls they replaced, token for token.
+#ifdef RTG_SHADE_SOBOL
+#define RTG_RNG_INC(pixel, sample, seed) sobol_inc(pixel, sample, seed)
+#define RTG_RNG_SEED(seed, inc) 0ull
+#define RTG_RNG_LOAD(x) sobol_load(x)
+#define RTG_RNG_RAW sobol_step
+#define RTG_RNG_NEXT sobol_next
+#define RTG_RNG_SAMPLER SobolSampler
+#else
+#define RTG_RNG_INC(pixel, sample, seed) pcg_inc(pixel, sample)
+#define RTG_RNG_SEED(seed, inc) pcg_seed(seed, inc)
+#define RTG_RNG_LOAD(x) x
+#define RTG_RNG_RAW pcg_step
+#define RTG_RNG_NEXT pcg_next
+#define RTG_RNG_SAMPLER PcgSampler
+#endif
     __shared__ unsigned s_cnt[2][RTG_TB / 64];
     __shared__ unsigned s_base[2];
     __shared__ float4 s_sho[RTG_TB], s_shd[RTG_TB];  // NEE ray staged until its queue position is known
@@ -147,8 +167,8 @@
             const int can_hit = lean0 ? 1 : (rd.w != 0.0f);  // canHitLight travels in ray_d.w
             unsigned lp, sl;
             split_pid(a, (unsigned)pid, lp, sl);
-            const uint64_t inc = pcg_inc(a.pixlist[lp], a.s0 + sl);  // (carrying it in the payload: slower)
-            uint64_t st = lean0 ? pcg_seed(a.seed, inc) : in_r[i];
+            const uint64_t inc = RTG_RNG_INC(a.pixlist[lp], a.s0 + sl, a.seed);  // (carrying it in the payload: slower)
+            uint64_t st = lean0 ? RTG_RNG_SEED(a.seed, inc) : RTG_RNG_LOAD(in_r[i]);
             v3 c = mk(0.0f, 0.0f, 0.0f);
             int nterms = b + 1;
             // state carried past the environment lookup: a miss, or a path-traced hit (stage 1:
@@ -243,8 +263,8 @@
                         float pmf;
                         int li;
                         if (PICK) {  // RTG_LIGHTS_POWER: r0, d1, always both
-                            const uint32_t r0 = pcg_step(st, inc);
-                            const float d1 = pcg_next(st, inc);
+                            const uint32_t r0 = RTG_RNG_RAW(st, inc);
+                            const float d1 = RTG_RNG_NEXT(st, inc);
 #ifdef RTG_SHADE_GRID
                             li = light_pick(lgr.table + light_grid_cell(lgr, x) * (uint32_t)nl, (uint32_t)nl, r0, d1, pmf);
 #else
@@ -252,7 +272,7 @@
 #endif
                         } else {
                             pmf = s.pmf;  // 1.f / (float)nl
-                            li = (int)((float)nl * pcg_next(st, inc));
+                            li = (int)((float)nl * RTG_RNG_NEXT(st, inc));
                             li = (nl - 1) < li ? (nl - 1) : li;
                         }
                         const DevLight L = TAB ? s_lt[li] : s.lights[li];
@@ -260,8 +280,8 @@
                         float pdf;
                         float env_flag = 0.0f;
                         if (__float_as_int(L.v1t.w) == 0) {
-                            const float r1 = pcg_next(st, inc);
-                            const float r2 = pcg_next(st, inc);
+                            const float r1 = RTG_RNG_NEXT(st, inc);
+                            const float r2 = RTG_RNG_NEXT(st, inc);
                             const float la = 1 - sqrtf(r1);
                             const float lb = r2 * sqrtf(r1);
                             const float lg = 1.0f - (la + lb);
@@ -293,14 +313,14 @@
                             v3 wi;
                             bool ok = true;
                             if (ENV) {  // RTG_ENV_LUMINANCE: r0, d1, d2, d3, always all four
-                                const uint32_t r0 = pcg_step(st, inc);
-                                const float d1 = pcg_next(st, inc);
-                                const float d2 = pcg_next(st, inc);
-                                const float d3 = pcg_next(st, inc);
+                                const uint32_t r0 = RTG_RNG_RAW(st, inc);
+                                const float d1 = RTG_RNG_NEXT(st, inc);
+                                const float d2 = RTG_RNG_NEXT(st, inc);
+                                const float d3 = RTG_RNG_NEXT(st, inc);
                                 ok = env_sample_luminance(et, r0, d1, d2, d3, wi, pdf);
                             } else {
-                                const float q2 = pcg_next(st, inc);
-                                const float q1 = pcg_next(st, inc);
+                                const float q2 = RTG_RNG_NEXT(st, inc);
+                                const float q1 = RTG_RNG_NEXT(st, inc);
                                 wi = uniform_sample_sphere(q1, q2);
                                 pdf = uniform_sphere_pdf();
                             }
@@ -322,7 +342,7 @@
                         // BSDF sample and its ray (Renderer.h:520-525)
                         v3 val;
                         float pdf_b;
-                        PcgSampler smp{st, inc};
+                        RTG_RNG_SAMPLER smp{st, inc};
                         const v3 wib = bsdf_sample(M.kind, M.int_ior, M.ext_ior, tex_sample(s, M, tu, tv), fr, wo, smp,
                                                    val, pdf_b);
                         st = smp.s;
@@ -360,21 +380,21 @@
                         float pmf = 0.0f;
                         int li;
                         if (PICK) {  // RTG_LIGHTS_POWER: r0, d1, always both
-                            const uint32_t r0 = pcg_step(st, inc);
-                            const float d1 = pcg_next(st, inc);
+                            const uint32_t r0 = RTG_RNG_RAW(st, inc);
+                            const float d1 = RTG_RNG_NEXT(st, inc);
 #ifdef RTG_SHADE_GRID
                             li = light_pick(lgr.table + light_grid_cell(lgr, x) * (uint32_t)nl, (uint32_t)nl, r0, d1, pmf);
 #else
                             li = light_pick(TAB ? s_pk : lpk.table, (uint32_t)nl, r0, d1, pmf);
 #endif
                         } else {
-                            li = (int)((float)nl * pcg_next(st, inc));
+                            li = (int)((float)nl * RTG_RNG_NEXT(st, inc));
                             li = (nl - 1) < li ? (nl - 1) : li;  // (std::min)(a, b)
                         }
                         const DevLight L = TAB ? s_lt[li] : s.lights[li];
                         if (__float_as_int(L.v1t.w) == 0) {  // AreaLight::sample -> Triangle::sample
-                            const float r1 = pcg_next(st, inc);
-                            const float r2 = pcg_next(st, inc);
+                            const float r1 = RTG_RNG_NEXT(st, inc);
+                            const float r2 = RTG_RNG_NEXT(st, inc);
                             const float la = 1 - sqrtf(r1);
                             const float lb = r2 * sqrtf(r1);
                             const float lg = 1.0f - (la + lb);
@@ -399,14 +419,14 @@
                             v3 wi;
                             bool ok = true;
                             if (ENV) {  // RTG_ENV_LUMINANCE: r0, d1, d2, d3, always all four
-                                const uint32_t r0 = pcg_step(st, inc);
-                                const float d1 = pcg_next(st, inc);
-                                const float d2 = pcg_next(st, inc);
-                                const float d3 = pcg_next(st, inc);
+                                const uint32_t r0 = RTG_RNG_RAW(st, inc);
+                                const float d1 = RTG_RNG_NEXT(st, inc);
+                                const float d2 = RTG_RNG_NEXT(st, inc);
+                                const float d3 = RTG_RNG_NEXT(st, inc);
                                 ok = env_sample_luminance(et, r0, d1, d2, d3, wi, l_pdf);
                             } else {
-                                const float q2 = pcg_next(st, inc);  // evaluated first -> r2
-                                const float q1 = pcg_next(st, inc);  // -> r1
+                                const float q2 = RTG_RNG_NEXT(st, inc);  // evaluated first -> r2
+                                const float q1 = RTG_RNG_NEXT(st, inc);  // -> r1
                                 wi = uniform_sample_sphere(q1, q2);
                                 l_pdf = uniform_sphere_pdf();
                             }
@@ -513,12 +533,12 @@
                 c = ld_pre ? cpre : mul(thr, mk(0.0f, 0.0f, 0.0f));
                 if ((!ALT || a.mode == RTG_INTEGRATOR_PATH) && b <= a.max_depth) {
                     const float rrp = wmin(lum(thr), 0.9f);
-                    if (pcg_next(st, inc) < rrp) {
+                    if (RTG_RNG_NEXT(st, inc) < rrp) {
                         thr = divs(thr, rrp);
                         // ---- BSDF::sample
                         v3 ind;
                         float pdf;
-                        PcgSampler smp{st, inc};
+                        RTG_RNG_SAMPLER smp{st, inc};
 #ifdef RTG_SHADE_PHYS
                         // the sample says whether it is specular (a delta lobe) and whether the path lives
                         bool sp = spec, live = true;
@@ -615,3 +635,9 @@
         }
         __syncthreads();
     }
+#undef RTG_RNG_INC
+#undef RTG_RNG_SEED
+#undef RTG_RNG_LOAD
+#undef RTG_RNG_RAW
+#undef RTG_RNG_NEXT
+#undef RTG_RNG_SAMPLER

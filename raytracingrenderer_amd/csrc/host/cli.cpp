@@ -42,6 +42,9 @@
 // Path-tracer MIS (rtg_set_path_mis): -pathMIS off|power (off: the reference's pathTrace; power: NEE and
 // BSDF-sampled emitter hits combined with the power heuristic, a miss weighted by the throughput), for one
 // device and for -gpus / -devices alike.
+// Sampler (rtg_set_sampler): -sampler pcg|sobol (pcg: one PCG32 stream per pixel and sample; sobol: an
+// Owen-scrambled Sobol sequence over the samples of a pixel, four dimensions per bounce), for one device
+// and for -gpus / -devices alike.
 // Camera pose (rtg_set_camera): -from "x y z" -to "x y z" -up "x y z" -fov degrees override scene.json's
 // pose through rth_camera_look_at, the loader's own camera code; each is optional and keeps the scene's
 // value when absent. For one device and for -gpus / -devices alike.
@@ -148,6 +151,9 @@ int main(int argc, char** argv) {
     const std::string pmn = get("-pathMIS", "off");
     if (pmn != "off" && pmn != "power") return die("-pathMIS", "one of off, power");
     const int path_mis = pmn == "power" ? RTG_PATH_MIS_POWER : RTG_PATH_MIS_OFF;
+    const std::string smn = get("-sampler", "pcg");
+    if (smn != "pcg" && smn != "sobol") return die("-sampler", "one of pcg, sobol");
+    const int sampler = smn == "sobol" ? RTG_SAMPLER_SOBOL : RTG_SAMPLER_PCG;
     uint32_t n_params = 0;
     const rtg_material_params* params = trn == "1" ? rth_scene_material_params_transmissive(scene, &n_params)
                                                    : rth_scene_material_params(scene, &n_params);
@@ -190,6 +196,7 @@ int main(int argc, char** argv) {
                          rtg_set_material_model(rt, RTG_MATERIALS_PHYSICAL) != 0))
             return die("rtg_set_material_model", rtg_last_error());
         if (rtg_set_path_mis(rt, path_mis) != 0) return die("rtg_set_path_mis", rtg_last_error());
+        if (rtg_set_sampler(rt, sampler) != 0) return die("rtg_set_sampler", rtg_last_error());
         if (pose_given && rtg_set_camera(rt, &new_cam, &new_proj) != 0) return die("rtg_set_camera", rtg_last_error());
     } else {
         if (rtg_group_create(devices.data(), (int)devices.size(), rth_scene_desc(scene), &grp) != 0)
@@ -203,6 +210,7 @@ int main(int argc, char** argv) {
                          rtg_group_set_material_model(grp, RTG_MATERIALS_PHYSICAL) != 0))
             return die("rtg_group_set_material_model", rtg_last_error());
         if (rtg_group_set_path_mis(grp, path_mis) != 0) return die("rtg_group_set_path_mis", rtg_last_error());
+        if (rtg_group_set_sampler(grp, sampler) != 0) return die("rtg_group_set_sampler", rtg_last_error());
         if (pose_given && rtg_group_set_camera(grp, &new_cam, &new_proj) != 0)
             return die("rtg_group_set_camera", rtg_last_error());
         std::printf("%d devices, own-tile film exchange by %s\n", (int)devices.size(),

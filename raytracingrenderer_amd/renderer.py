@@ -355,6 +355,26 @@ def path_mis_check(mode):
     _check(lib.rtg_path_mis_check(_path_mis(mode)), lib.rtg_last_error)
 
 
+SAMPLERS = {"pcg": N.RTG_SAMPLER_PCG, "sobol": N.RTG_SAMPLER_SOBOL}
+
+
+def _sampler(name):
+    """The RTG_SAMPLER_* value of set_sampler's argument (a name of SAMPLERS or a value; an unknown value
+    is the library's error)."""
+    if isinstance(name, str):
+        if name not in SAMPLERS:
+            raise ValueError("unknown sampler %r (one of %s)" % (name, ", ".join(SAMPLERS)))
+        return SAMPLERS[name]
+    return int(name)
+
+
+def sampler_check(name):
+    """rtg_set_sampler's argument check alone (rtg_sampler_check; no GPU): raises NativeError for an
+    unknown value."""
+    lib = N.rtg()
+    _check(lib.rtg_sampler_check(_sampler(name)), lib.rtg_last_error)
+
+
 def mis_weight_probe(p, q):
     """The path-tracer MIS kernels' own weight function (rtg_probe_mis_weight, test surface) on the
     current device: mis_w(p[i], q[i]) for p, q (n,) float32."""
@@ -811,6 +831,31 @@ class RayTracer:
 
     mis_weight_probe = staticmethod(mis_weight_probe)
 
+    def set_sampler(self, name="pcg"):
+        """Where the random numbers of a path and of a camera sample come from (rtg_set_sampler). "pcg"
+        (default): one PCG32 stream per (pixel, sample), today's films bit for bit. "sobol": Burley's
+        hash-based Owen-scrambled Sobol sequence, padded 4-D (include/rtg.h has the definition): the
+        samples of a pixel are stratified against each other in every group of four draws; no estimator
+        changes. Applies to render(), adaptiveRender() and the "path", "direct" and "direct_mis"
+        integrators, with either environment mode, the uniform and power light picks and camera sampling;
+        frames under the light grid, the physical material model or path MIS keep "pcg", as
+        lightTracer() and instantRadiosity() do (sampler_active tells)."""
+        _check(self._lib.rtg_set_sampler(self._h, _sampler(name)), self._lib.rtg_last_error)
+
+    @property
+    def sampler(self):
+        """The current setting, "pcg" or "sobol"."""
+        m = C.c_int()
+        _check(self._lib.rtg_get_sampler(self._h, C.byref(m)), self._lib.rtg_last_error)
+        return {v: k for k, v in SAMPLERS.items()}.get(m.value, m.value)
+
+    @property
+    def sampler_active(self):
+        """What the next render() would draw from under the handle's other settings (rtg_sampler_active)."""
+        m = C.c_int()
+        _check(self._lib.rtg_sampler_active(self._h, C.byref(m)), self._lib.rtg_last_error)
+        return {v: k for k, v in SAMPLERS.items()}.get(m.value, m.value)
+
     def env_pdf(self, dirs):
         """The solid-angle density the current environment mode gives directions (n, 3)
         (rtg_probe_env_pdf): the luminance table's cell density over sin theta, or 1 / (4 pi)."""
@@ -1080,6 +1125,10 @@ class RayTracerGroup:
     def set_path_mis(self, mode="off"):
         """RayTracer.set_path_mis on every rank (rtg_group_set_path_mis)."""
         _check(self._lib.rtg_group_set_path_mis(self._g, _path_mis(mode)), self._lib.rtg_last_error)
+
+    def set_sampler(self, name="pcg"):
+        """RayTracer.set_sampler on every rank (rtg_group_set_sampler)."""
+        _check(self._lib.rtg_group_set_sampler(self._g, _sampler(name)), self._lib.rtg_last_error)
 
     def set_material_model(self, mode="reference", transmission=False):
         """RayTracer.set_material_model on every rank (rtg_group_set_material_params / _model)."""

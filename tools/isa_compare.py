@@ -49,7 +49,7 @@ def kernels_of(asm):
     md = md[:md.index("amdhsa.target")]
     entries = {}
     for blk in re.split(r"\n  - ", md)[1:]:
-        entries[re.search(r"\.symbol:\s+(\S+)\.kd", blk).group(1)] = blk
+        entries[re.search(r"\.symbol:\s+(\S+)\.kd", blk).group(1)] = blk.rstrip("\n")  # (the unit's last entry ends the list)
     out = {}
     for sym, blk in entries.items():
         m = re.search(r"^%s:.*?^\.Lfunc_end\d+:" % re.escape(sym), asm, re.S | re.M)

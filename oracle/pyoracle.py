@@ -51,6 +51,20 @@ def lib(flavour="rtm"):
         L.or_set_env_table.argtypes = [vp, u32p, C.c_uint32, C.c_uint32]
         L.or_env_counts.restype = C.c_int
         L.or_env_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
+        L.or_set_light_table.restype = C.c_int
+        L.or_set_light_table.argtypes = [vp, u32p, C.c_uint32]
+        L.or_set_light_grid.restype = C.c_int
+        L.or_set_light_grid.argtypes = [vp, u32p, u32p, f32p, f32p]
+        L.or_set_sampler.restype = C.c_int
+        L.or_set_sampler.argtypes = [vp, C.c_int]
+        L.or_mode_counts.restype = C.c_int
+        L.or_mode_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
+        L.or_sampler_draws.restype = C.c_int
+        L.or_sampler_draws.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_uint32, u32p]
+        L.or_sobol_draws.restype = C.c_int
+        L.or_sobol_draws.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p]
+        L.or_sobol_mix32.restype = C.c_uint32
+        L.or_sobol_mix32.argtypes = [C.c_uint32]
         for fn in ("or_acosf", "or_sinf", "or_cosf"):
             getattr(L, fn).restype = C.c_float
             getattr(L, fn).argtypes = [C.c_float]
@@ -111,6 +125,55 @@ class Oracle:
         out = np.zeros(len(self.ENV_COUNTS), np.uint64)
         self.L.or_env_counts(self.h, _p(out, C.c_uint64), 1 if reset else 0)
         return dict(zip(self.ENV_COUNTS, (int(v) for v in out)))
+
+    MODE_COUNTS = ("picks", "alias_picks", "picks_deep", "nee_deep", "other_cell", "other_cells_distinct", "mis_emitter",
+                   "sobol_rounded", "sobol_aligned", "sobol_max_group")
+    SAMPLERS = {"pcg": 0, "sobol": 1}
+
+    def set_light_table(self, entries):
+        """RTG_LIGHTS_POWER with the alias table `entries` ((n_lights, 4) uint32 words: prob, alias,
+        pmf_self, pmf_alias); None: the uniform pick again (and no grid)."""
+        if entries is None:
+            self.L.or_set_light_table(self.h, None, 0)
+            return
+        e = np.ascontiguousarray(entries, np.uint32).reshape(-1, 4)
+        if self.L.or_set_light_table(self.h, _p(e, C.c_uint32), len(e)) != 0:
+            raise ValueError("or_set_light_table: bad argument")
+
+    def set_light_grid(self, entries, dims=None, lo=None, scale=None):
+        """rtg_set_light_grid with the tables `entries` ((cells, n_lights, 4) uint32 words) and the kernel's
+        constants dims[3], lo[3], scale[3]; None: off. Needs a light table."""
+        if entries is None:
+            self.L.or_set_light_grid(self.h, None, None, None, None)
+            return
+        e = np.ascontiguousarray(entries, np.uint32)
+        d = np.ascontiguousarray(dims, np.uint32).reshape(-1)
+        l, sc = (np.ascontiguousarray(v, np.float32).reshape(-1) for v in (lo, scale))
+        if (len(d) != 3 or len(l) != 3 or len(sc) != 3 or e.ndim != 3 or e.shape[0] != int(np.prod(d.astype(np.int64)))
+                or e.shape[2] != 4 or e.shape[1] != len(self.scene.lights)
+                or self.L.or_set_light_grid(self.h, _p(e, C.c_uint32), _p(d, C.c_uint32), _p(l, C.c_float), _p(sc, C.c_float)) != 0):
+            raise ValueError("or_set_light_grid: bad argument")
+
+    def set_sampler(self, sampler="pcg"):
+        """rtg_set_sampler for render, render_adaptive, trace_paths, path_events and camera_rays' per-sample
+        form: "pcg" or "sobol" (the light tracer and instant radiosity keep PCG)."""
+        v = self.SAMPLERS.get(sampler, -1) if isinstance(sampler, str) else int(sampler)
+        if self.L.or_set_sampler(self.h, v) != 0:
+            raise ValueError("or_set_sampler: bad argument")
+
+    def mode_counts(self, reset=True):
+        """{name: count} of what the light picks and the Sobol sampler met since the last reset."""
+        out = np.zeros(len(self.MODE_COUNTS), np.uint64)
+        self.L.or_mode_counts(self.h, _p(out, C.c_uint64), 1 if reset else 0)
+        return dict(zip(self.MODE_COUNTS, (int(v) for v in out)))
+
+    def sampler_draws(self, pixel, sample, seed=1234, n=16, camera=False):
+        """The first n raw 32-bit draws of the path's (or the camera sample's) stream of (pixel, sample)
+        under the current sampler, the counter not rounded in between."""
+        out = np.zeros(n, np.uint32)
+        if self.L.or_sampler_draws(self.h, pixel, sample, seed, 1 if camera else 0, n, _p(out, C.c_uint32)) != 0:
+            raise ValueError("or_sampler_draws: bad argument")
+        return out
 
     def render(self, n_samples, first=0, seed=1234, tiles=None, threads=1, film=None, count=False):
         if film is None:
@@ -197,7 +260,9 @@ class Oracle:
 
     EVENT_KINDS = {1: "closest hit (id, t, alpha, beta)", 2: "light sample (index, point/direction)",
                    3: "shadow ray (visible, maxT)", 4: "russian roulette (draw, probability, depth)",
-                   5: "BSDF sample (wi, pdf)", 6: "luminance-mode environment sample (pdf, accepted)"}
+                   5: "BSDF sample (wi, pdf)", 6: "luminance-mode environment sample (pdf, accepted)",
+                   7: "light pick from a table (slot, light, pmf, grid cell)",
+                   8: "Sobol bounce (counter as loaded, counter after rounding, depth)"}
 
     def path_events(self, pixel, sample, seed=1234, cap=256):
         """Event list of one path (or_path_events): (events[n, 5], radiance[3])."""

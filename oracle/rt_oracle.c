@@ -26,8 +26,14 @@
  * The two opt-in sampling modes of include/rtg.h, which the reference does not have, are restated from
  * that header's definition (not from the device code): or_set_camera_sampling (pixel-filter jitter and
  * the thin lens, a camera ray per sample) and or_set_env_table (RTG_ENV_LUMINANCE: the environment
- * branches of computeDirect and computeDirectMIS sample a caller-given alias table). Unset, every
- * function below is the reference's.
+ * branches of computeDirect and computeDirectMIS sample a caller-given alias table). So are three further
+ * opt-in modes: or_set_light_table (RTG_LIGHTS_POWER: the light of an NEE sample comes from a caller-given
+ * alias table over the light list, two draws in the uniform pick's one's place), or_set_light_grid
+ * (rtg_set_light_grid: the table is the one of the grid cell that holds the shading point) and
+ * or_set_sampler (RTG_SAMPLER_SOBOL: the path's and the camera sample's draws are Owen-scrambled Sobol
+ * points, the draw counter rounded up to a multiple of four when a bounce past the camera's opens).
+ * or_mode_counts says what a render under them met, or_path_events logs the picks and the counter,
+ * or_sampler_draws and or_sobol_draws expose the streams. Unset, every function below is the reference's.
  *
  * Argument-evaluation order: the reference writes cosineSampleHemisphere(sampler.next(),
  * sampler.next()) (Materials.h:129) and uniformSampleSphere(sampler.next(), sampler.next())
@@ -124,7 +130,93 @@ static void pcg_init(Pcg* p, uint64_t seed, uint64_t seq) {
     p->s += seed;
     pcg_u32(p);
 }
-static float pcg_next(Pcg* p) { return (float)(pcg_u32(p) >> 8) * (1.0f / 16777216.0f); }
+/* (the float draw, (float)(u32 >> 8) * 2^-24, is smp_next below: one conversion for both samplers) */
+
+/* RTG_SAMPLER_SOBOL (include/rtg.h, "the sampler"): Burley's hash-based Owen-scrambled Sobol sequence,
+ * padded 4-D, restated from the header's definition. uint32 arithmetic with wrap-around. */
+static uint32_t sb_mix32(uint32_t x) {
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+static uint32_t sb_lk(uint32_t x, uint32_t s) {
+    x += s; x ^= x * 0x6c50b47cu; x ^= x * 0xb82f1e52u; x ^= x * 0xc7afe638u; x ^= x * 0x8d22f6e6u;
+    return x;
+}
+static uint32_t sb_brev(uint32_t x) {
+    x = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
+    x = ((x >> 2) & 0x33333333u) | ((x & 0x33333333u) << 2);
+    x = ((x >> 4) & 0x0F0F0F0Fu) | ((x & 0x0F0F0F0Fu) << 4);
+    x = ((x >> 8) & 0x00FF00FFu) | ((x & 0x00FF00FFu) << 8);
+    return (x >> 16) | (x << 16);
+}
+static uint32_t sb_owen(uint32_t x, uint32_t s) { return sb_brev(sb_lk(sb_brev(x), s)); }
+static uint32_t sb_key(uint32_t pixel, uint64_t seed, uint32_t stream) {
+    return sb_mix32(pixel ^ sb_mix32((uint32_t)seed ^ sb_mix32((uint32_t)(seed >> 32) ^ stream)));
+}
+/* D_1, D_2, D_3 by the Joe-Kuo recurrence from (degree, a, m) = 1/0/(1), 2/1/(1,3), 3/1/(1,3,1), as the
+ * header names them (its listed words are checked against this by tests/test_oracle_modes.py through the
+ * header's check values); D_0[b] = 0x80000000 >> b. */
+static uint32_t g_sb_dir[4][16];
+static void sb_tables(void) {
+    static const int deg[4] = {0, 1, 2, 3}, a_[4] = {0, 0, 1, 1};
+    static const uint32_t m0[4][3] = {{0, 0, 0}, {1, 0, 0}, {1, 3, 0}, {1, 3, 1}};
+    for (int b = 0; b < 16; ++b) g_sb_dir[0][b] = 0x80000000u >> b;
+    for (int c = 1; c < 4; ++c) {
+        uint32_t m[16];
+        int d = deg[c];
+        for (int i = 0; i < d; ++i) m[i] = m0[c][i];
+        for (int i = d; i < 16; ++i) {
+            uint32_t v = m[i - d] ^ (m[i - d] << d);
+            for (int k = 1; k < d; ++k)
+                if ((a_[c] >> (d - 1 - k)) & 1) v ^= m[i - k] << k;
+            m[i] = v;
+        }
+        for (int i = 0; i < 16; ++i) g_sb_dir[c][i] = m[i] << (31 - i);
+    }
+}
+static pthread_once_t g_sb_once = PTHREAD_ONCE_INIT;
+/* raw draw n of (key, sample) */
+static uint32_t sb_draw(uint32_t key, uint32_t sample, uint32_t n) {
+    uint32_t g = n >> 2, c = n & 3u;
+    uint32_t gs = sb_mix32(key ^ (g * 0x9E3779B9u));
+    uint32_t idx = sb_owen(sample, gs) & 0xFFFFu;
+    uint32_t x = 0;
+    for (int b = 0; b < 16; ++b)
+        if ((idx >> b) & 1u) x ^= g_sb_dir[c][b];
+    return sb_owen(x, sb_mix32(gs + (c + 1u) * 0x85EBCA6Bu));
+}
+
+/* The path's generator: the PCG stream or, under or_set_sampler(RTG_SAMPLER_SOBOL), the draw counter n of
+ * (key, sample). Every draw of computeDirect, computeDirectMIS, BSDF::sample and the roulette goes through
+ * smp_u32 (the raw 32-bit draw) or smp_next (the float draw; the same conversion in both modes). */
+typedef struct {
+    Pcg p;
+    int sobol;
+    uint32_t key, sample, n, max_n; /* max_n: the highest draw index taken, plus one */
+} Smp;
+static __attribute__((noinline, cold)) uint32_t smp_sobol_u32(Smp* q) {
+    uint32_t x = sb_draw(q->key, q->sample, q->n++);
+    if (q->n > q->max_n) q->max_n = q->n;
+    return x;
+}
+/* (the Sobol draw stays out of line, so that the default's draw sites inline the PCG step as they did) */
+static inline uint32_t smp_u32(Smp* q) {
+    if (__builtin_expect(q->sobol, 0)) return smp_sobol_u32(q);
+    return pcg_u32(&q->p);
+}
+static inline float smp_next(Smp* q) { return (float)(smp_u32(q) >> 8) * (1.0f / 16777216.0f); }
+static void smp_init_pcg(Smp* q, uint64_t seed, uint64_t seq) {
+    q->sobol = 0;
+    q->key = q->sample = q->n = q->max_n = 0;
+    pcg_init(&q->p, seed, seq);
+}
+static void smp_init_sobol(Smp* q, uint32_t pixel, uint32_t sample, uint64_t seed, uint32_t stream) {
+    q->sobol = 1;
+    q->p.s = q->p.inc = 0;
+    q->key = sb_key(pixel, seed, stream);
+    q->sample = sample;
+    q->n = q->max_n = 0;
+}
 
 /* ------------------------------------------------------------------ scene */
 /* Scene records in the reference's memory layout, so that the tile renderer's cache behaviour (and
@@ -159,6 +251,13 @@ struct or_scene {
     uint32_t* env_tab;       /* or_set_env_table: env_w * env_h entries of 4 words, or NULL (uniform) */
     uint32_t env_w, env_h;
     uint64_t* env_cnt;       /* or_env_counts: what the luminance-mode samples met (OR_ENV_*) */
+    uint32_t* light_tab;     /* or_set_light_table: nlight entries of 4 words, or NULL (the uniform pick) */
+    uint32_t* grid_tab;      /* or_set_light_grid: cells * nlight entries of 4 words, or NULL */
+    uint32_t grid_dims[3];
+    float grid_lo[3], grid_scale[3];
+    int sobol;               /* or_set_sampler: RTG_SAMPLER_SOBOL */
+    uint64_t* mode_cnt;      /* or_mode_counts (OR_MODE_*) */
+    uint8_t* cell_seen;      /* per grid cell: a pick at depth >= 1 outside the camera hit's cell fell here */
 };
 
 /* Counters of the luminance-mode environment samples (or_env_counts), so that a test can assert that a
@@ -166,6 +265,15 @@ struct or_scene {
 enum { OR_ENV_SAMPLES, OR_ENV_REJECTED, OR_ENV_OCCLUDED, OR_ENV_PATHS_TWO, OR_ENV_MIS_EMITTER, OR_ENV_MIS_EMITTER_REJ, OR_ENV_NCOUNT };
 static __thread int g_path_env; /* environment samples of the current path */
 static void env_count(const struct or_scene* s, int what) { __sync_fetch_and_add(&s->env_cnt[what], (uint64_t)1); }
+
+/* Counters of the light pick and the Sobol sampler (or_mode_counts), for the same purpose. They are touched
+ * only while a light table or the Sobol sampler is set. */
+enum { OR_MODE_PICKS, OR_MODE_ALIAS, OR_MODE_PICKS_DEEP, OR_MODE_NEE_DEEP, OR_MODE_OTHER_CELL, OR_MODE_OTHER_CELLS_DISTINCT,
+       OR_MODE_MIS_EMITTER, OR_MODE_SOBOL_ROUNDED, OR_MODE_SOBOL_ALIGNED, OR_MODE_SOBOL_MAX_GROUP, OR_MODE_NCOUNT };
+static __thread int g_depth;         /* depth of the current shading event (0: the camera hit) */
+static __thread uint32_t g_cam_cell; /* grid cell of the current path's camera hit */
+static void mode_count(const struct or_scene* s, int what) { __sync_fetch_and_add(&s->mode_cnt[what], (uint64_t)1); }
+static int modes_on(const struct or_scene* s) { return s->light_tab != NULL || s->sobol; }
 
 typedef struct {
     uint64_t ext_rays, shadow_rays, nodes, tris;
@@ -416,11 +524,11 @@ static int env_sample_table(const struct or_scene* s, uint32_t r0, float d1, flo
     return 1;
 }
 /* The four draws of the luminance-mode environment branch, in the header's order, and the sample. */
-static int env_light_sample(const struct or_scene* s, Pcg* smp, int li, V3* wi, float* pdf) {
-    uint32_t r0 = pcg_u32(smp);
-    float d1 = pcg_next(smp);
-    float d2 = pcg_next(smp);
-    float d3 = pcg_next(smp);
+static int env_light_sample(const struct or_scene* s, Smp* smp, int li, V3* wi, float* pdf) {
+    uint32_t r0 = smp_u32(smp);
+    float d1 = smp_next(smp);
+    float d2 = smp_next(smp);
+    float d3 = smp_next(smp);
     int ok = env_sample_table(s, r0, d1, d2, d3, wi, pdf);
     ev_push(2, (float)li, wi->x, wi->y, wi->z); /* environment sample direction */
     ev_push(6, *pdf, (float)ok, 0, 0);          /* its pdf (0: rejected) */
@@ -430,17 +538,70 @@ static int env_light_sample(const struct or_scene* s, Pcg* smp, int li, V3* wi, 
     return ok;
 }
 
+/* rtg_set_light_grid's cell of a point (include/rtg.h, "cell of x"): float32 in the order written, the
+ * clamp by fmaxf / fminf, a NaN giving 0. */
+static uint32_t grid_axis(float x, float lo, float scale, uint32_t dim) {
+    float u = (x - lo) * scale;
+    return (uint32_t)(int)fminf(fmaxf(u, 0.0f), (float)(dim - 1u));
+}
+static uint32_t grid_cell(const struct or_scene* s, V3 x) {
+    uint32_t ix = grid_axis(x.x, s->grid_lo[0], s->grid_scale[0], s->grid_dims[0]);
+    uint32_t iy = grid_axis(x.y, s->grid_lo[1], s->grid_scale[1], s->grid_dims[1]);
+    uint32_t iz = grid_axis(x.z, s->grid_lo[2], s->grid_scale[2], s->grid_dims[2]);
+    return (iz * s->grid_dims[1] + iy) * s->grid_dims[0] + ix;
+}
+/* Scene::sampleLight (Scene.h:137-138): the light of an NEE sample at the shading point x and its pmf.
+ * Default: li = (int)(n * u) clamped, pmf = 1 / n, one draw. Under or_set_light_table (RTG_LIGHTS_POWER,
+ * include/rtg.h "draws" and "pick"): r0, a raw draw, then d1, a float draw, always both; the entry
+ * k = (r0 * n) >> 32 of the table, or under or_set_light_grid of the table of the cell that holds x. */
+static int pick_light(const struct or_scene* s, V3 x, Smp* smp, float* pmf) {
+    if (!s->light_tab) {
+        *pmf = 1.f / (float)s->nlight;
+        int li = (int)((float)s->nlight * smp_next(smp));
+        if (s->nlight - 1 < li) li = s->nlight - 1; /* (std::min)(a, b) */
+        return li;
+    }
+    uint32_t n = (uint32_t)s->nlight;
+    uint32_t r0 = smp_u32(smp);
+    float d1 = smp_next(smp);
+    uint32_t cell = 0;
+    const uint32_t* tab = s->light_tab;
+    if (s->grid_tab) {
+        cell = grid_cell(s, x);
+        tab = s->grid_tab + (size_t)cell * n * 4;
+    }
+    uint32_t k = (uint32_t)(((uint64_t)r0 * n) >> 32);
+    const uint32_t* e = tab + (size_t)k * 4;
+    float prob, pmf_self, pmf_alias;
+    memcpy(&prob, &e[0], 4);
+    memcpy(&pmf_self, &e[2], 4);
+    memcpy(&pmf_alias, &e[3], 4);
+    int keep = d1 < prob;
+    int li = (int)(keep ? k : e[1]);
+    *pmf = keep ? pmf_self : pmf_alias;
+    ev_push(7, (float)k, (float)li, *pmf, (float)cell); /* light pick */
+    mode_count(s, OR_MODE_PICKS);
+    if (!keep) mode_count(s, OR_MODE_ALIAS);
+    if (g_depth >= 1) {
+        mode_count(s, OR_MODE_PICKS_DEEP);
+        if (s->grid_tab && cell != g_cam_cell) {
+            mode_count(s, OR_MODE_OTHER_CELL);
+            __atomic_store_n(&s->cell_seen[cell], (uint8_t)1, __ATOMIC_RELAXED); /* (render threads share it) */
+        }
+    }
+    return li;
+}
+
 /* RayTracer::computeDirect (Renderer.h:423-473) */
-static Col compute_direct(const struct or_scene* s, const Shading* sd, Pcg* smp, Counts* c) {
+static Col compute_direct(const struct or_scene* s, const Shading* sd, Smp* smp, Counts* c) {
     if (is_spec(sd->bsdf)) return col(0.0f, 0.0f, 0.0f);
-    float pmf = 1.f / (float)s->nlight;
-    int li = (int)((float)s->nlight * pcg_next(smp));
-    if (s->nlight - 1 < li) li = s->nlight - 1; /* (std::min)(a, b) */
+    float pmf;
+    int li = pick_light(s, sd->x, smp, &pmf);
     int lt = s->light[li];
     if (lt >= 0) { /* AreaLight::sample -> Triangle::sample (Geometry.h:114-126) */
         const Tri* T = &s->tri[lt];
-        float r1 = pcg_next(smp);
-        float r2 = pcg_next(smp);
+        float r1 = smp_next(smp);
+        float r2 = smp_next(smp);
         float alpha = 1 - sqrtf(r1);
         float beta = r2 * sqrtf(r1);
         float gamma = 1.0f - (alpha + beta);
@@ -471,8 +632,8 @@ static Col compute_direct(const struct or_scene* s, const Shading* sd, Pcg* smp,
             }
         }
     } else { /* EnvironmentMap::sample */
-        float q2 = pcg_next(smp);
-        float q1 = pcg_next(smp);
+        float q2 = smp_next(smp);
+        float q1 = smp_next(smp);
         V3 wi = uniform_sample_sphere(q1, q2);
         ev_push(2, (float)li, wi.x, wi.y, wi.z); /* environment sample direction */
         float pdf = (float)(1.0f / (4.0f * O_PI));
@@ -499,12 +660,12 @@ static float area_to_solid(float pdf_area, float dist2, float cos_theta) {
 static float balance(float pa, float pb) { return pa / (pa + pb); }
 
 /* BSDF::sample for the three effective behaviours */
-static V3 bsdf_sample(const struct or_scene* s, const Shading* sd, Pcg* smp, Col* refl, float* pdf) {
+static V3 bsdf_sample(const struct or_scene* s, const Shading* sd, Smp* smp, Col* refl, float* pdf) {
     const rtg_material* m = sd->bsdf;
     Col alb = tex_sample(s, m->texture, sd->tu, sd->tv);
     if (m->kind == RTG_MAT_DIFFUSE || m->kind == RTG_MAT_LAMBERT) {
-        float q2 = pcg_next(smp); /* cosineSampleHemisphere(sampler.next(), sampler.next()) */
-        float q1 = pcg_next(smp);
+        float q2 = smp_next(smp); /* cosineSampleHemisphere(sampler.next(), sampler.next()) */
+        float q1 = smp_next(smp);
         V3 wl = cosine_sample_hemisphere(q1, q2);
         if (m->kind == RTG_MAT_DIFFUSE) *pdf = (float)((wl.z >= 0.0f) ? (wl.z / O_PI) : 0.0f); /* cosineHemispherePDF */
         else *pdf = (float)(wl.z / O_PI);                                                      /* Lambert stubs */
@@ -526,7 +687,7 @@ static V3 bsdf_sample(const struct or_scene* s, const Shading* sd, Pcg* smp, Col
     V3 wt = v3(0, 0, 0), wi;
     float R = fresnel_dielectric(cos_i, eta_i, eta_t, &wt, wol);
     if (!enter) wt.z = -wt.z;
-    int reflect = (R == 1.0f || pcg_next(smp) < R);
+    int reflect = (R == 1.0f || smp_next(smp) < R);
     if (reflect) {
         wi = v3(-wol.x, -wol.y, wol.z);
         *pdf = R;
@@ -540,19 +701,18 @@ static V3 bsdf_sample(const struct or_scene* s, const Shading* sd, Pcg* smp, Col
 }
 
 /* RayTracer::computeDirectMIS (Renderer.h:474-557) */
-static Col compute_direct_mis(const struct or_scene* s, const Shading* sd, Pcg* smp, Counts* c) {
+static Col compute_direct_mis(const struct or_scene* s, const Shading* sd, Smp* smp, Counts* c) {
     if (is_spec(sd->bsdf)) return col(0.0f, 0.0f, 0.0f);
     Col result = col(0.0f, 0.0f, 0.0f);
-    float pmf = 1.f / (float)s->nlight;
-    int li = (int)((float)s->nlight * pcg_next(smp));
-    if (s->nlight - 1 < li) li = s->nlight - 1;
+    float pmf; /* (the BSDF half below reuses pdf * pmf of this, the sampled, light: include/rtg.h "DIRECT_MIS") */
+    int li = pick_light(s, sd->x, smp, &pmf);
     int lt = s->light[li];
     float pdf;
     int env_sampled = 0;
     if (lt >= 0) {
         const Tri* T = &s->tri[lt];
-        float r1 = pcg_next(smp);
-        float r2 = pcg_next(smp);
+        float r1 = smp_next(smp);
+        float r2 = smp_next(smp);
         float alpha = 1 - sqrtf(r1);
         float beta = r2 * sqrtf(r1);
         float gamma = 1.0f - (alpha + beta);
@@ -591,8 +751,8 @@ static Col compute_direct_mis(const struct or_scene* s, const Shading* sd, Pcg* 
             }
         }
     } else {
-        float q2 = pcg_next(smp);
-        float q1 = pcg_next(smp);
+        float q2 = smp_next(smp);
+        float q1 = smp_next(smp);
         V3 wi = uniform_sample_sphere(q1, q2);
         pdf = (float)(1.0f / (4.0f * O_PI));
         Col emitted = env_eval(s, wi);
@@ -616,6 +776,7 @@ static Col compute_direct_mis(const struct or_scene* s, const Shading* sd, Pcg* 
                 env_count(s, OR_ENV_MIS_EMITTER);
                 if (!(pdf > 0)) env_count(s, OR_ENV_MIS_EMITTER_REJ);
             }
+            if (s->light_tab) mode_count(s, OR_MODE_MIS_EMITTER);
             V3 wi = vsub(sl.x, sd->x);
             float dist2 = vlen2(wi);
             wi = vnorm(wi);
@@ -629,7 +790,7 @@ static Col compute_direct_mis(const struct or_scene* s, const Shading* sd, Pcg* 
 }
 
 /* RayTracer::pathTrace (Renderer.h:328-392) */
-static Col path_trace(const struct or_scene* s, Ray* r, Col* thr, int depth, Pcg* smp, int can_hit, Counts* c) {
+static Col path_trace(const struct or_scene* s, Ray* r, Col* thr, int depth, Smp* smp, int can_hit, Counts* c) {
     Isect is = scene_traverse(s, r, c);
     Shading sd = shading_data(s, &is, r);
     if (sd.t < FLT_MAX) {
@@ -640,10 +801,22 @@ static Col path_trace(const struct or_scene* s, Ray* r, Col* thr, int depth, Pcg
             }
             return col(0.0f, 0.0f, 0.0f);
         }
+        if (modes_on(s)) {
+            g_depth = depth;
+            if (depth == 0 && s->grid_tab) g_cam_cell = grid_cell(s, sd.x);
+            if (depth >= 1 && smp->sobol) { /* a bounce past the camera's opens on a fresh 4-D point */
+                uint32_t loaded = smp->n;
+                smp->n = (loaded + 3u) & ~3u;
+                ev_push(8, (float)loaded, (float)smp->n, (float)depth, 0); /* Sobol bounce */
+                mode_count(s, (loaded & 3u) ? OR_MODE_SOBOL_ROUNDED : OR_MODE_SOBOL_ALIGNED);
+            }
+        }
         Col direct = cmul(*thr, compute_direct(s, &sd, smp, c));
+        if (depth >= 1 && modes_on(s) && (direct.r != 0.0f || direct.g != 0.0f || direct.b != 0.0f))
+            mode_count(s, OR_MODE_NEE_DEEP); /* (not zero: the sample was visible) */
         if (depth > s->max_depth) return direct;
         float rrp = win_min(clum(*thr), 0.9f);
-        float q = pcg_next(smp);
+        float q = smp_next(smp);
         ev_push(4, q, rrp, (float)depth, 0); /* Russian roulette */
         if (q < rrp) *thr = cdivs(*thr, rrp);
         else return direct;
@@ -690,12 +863,13 @@ static int camera_per_sample(const struct or_scene* s) { return s->cs.filter != 
  * four draws from the camera's own stream, always all four; the film position goes to fxy (or NULL). */
 static Ray camera_ray_sampled(const struct or_scene* s, uint32_t pixel, uint32_t sample, uint64_t seed, float* fxy) {
     uint32_t x = pixel % (uint32_t)s->W, y = pixel / (uint32_t)s->W;
-    Pcg cs;
-    pcg_init(&cs, seed ^ 0x9E3779B97F4A7C15ULL, ((uint64_t)pixel << 16) | sample);
-    float u0 = pcg_next(&cs);
-    float u1 = pcg_next(&cs);
-    float u2 = pcg_next(&cs);
-    float u3 = pcg_next(&cs);
+    Smp cs; /* RTG_SAMPLER_SOBOL: draws 0..3 of the camera stream, one 4-D point */
+    if (s->sobol) smp_init_sobol(&cs, pixel, sample, seed, 0x9E3779B9u);
+    else smp_init_pcg(&cs, seed ^ 0x9E3779B97F4A7C15ULL, ((uint64_t)pixel << 16) | sample);
+    float u0 = smp_next(&cs);
+    float u1 = smp_next(&cs);
+    float u2 = smp_next(&cs);
+    float u3 = smp_next(&cs);
     float px = ((float)x + 0.5f) + filter_offset(s->cs.filter, s->cs.filter_radius, u0);
     float py = ((float)y + 0.5f) + filter_offset(s->cs.filter, s->cs.filter_radius, u1);
     if (fxy) { fxy[0] = px; fxy[1] = py; }
@@ -716,7 +890,7 @@ static Ray camera_ray_sampled(const struct or_scene* s, uint32_t pixel, uint32_t
 }
 
 /* RayTracer::direct (Renderer.h:393-407): emission or one NEE sample at the first hit; 0 on a miss */
-static Col direct_only(const struct or_scene* s, Ray* r, Pcg* smp, Counts* c) {
+static Col direct_only(const struct or_scene* s, Ray* r, Smp* smp, Counts* c) {
     Isect is = scene_traverse(s, r, c);
     Shading sd = shading_data(s, &is, r);
     if (sd.t < FLT_MAX) {
@@ -727,7 +901,7 @@ static Col direct_only(const struct or_scene* s, Ray* r, Pcg* smp, Counts* c) {
 }
 
 /* RayTracer::direct with computeDirectMIS in place of computeDirect */
-static Col direct_mis_only(const struct or_scene* s, Ray* r, Pcg* smp, Counts* c) {
+static Col direct_mis_only(const struct or_scene* s, Ray* r, Smp* smp, Counts* c) {
     Isect is = scene_traverse(s, r, c);
     Shading sd = shading_data(s, &is, r);
     if (sd.t < FLT_MAX) {
@@ -764,18 +938,30 @@ static Col normals_only(const struct or_scene* s, Ray* r, Counts* c) {
 
 static Col pixel_sample(const struct or_scene* s, uint32_t pixel, uint32_t sample, uint64_t seed, Counts* c) {
     uint32_t x = pixel % (uint32_t)s->W, y = pixel / (uint32_t)s->W;
-    Pcg smp;
-    pcg_init(&smp, seed, ((uint64_t)pixel << 16) | sample);
+    Smp smp;
+    if (s->sobol) smp_init_sobol(&smp, pixel, sample, seed, 0u);
+    else smp_init_pcg(&smp, seed, ((uint64_t)pixel << 16) | sample);
     Ray r = camera_per_sample(s) ? camera_ray_sampled(s, pixel, sample, seed, NULL) : camera_ray(s, x + 0.5f, y + 0.5f);
     Col thr = col(1.0f, 1.0f, 1.0f);
+    Col L;
     g_path_env = 0;
+    g_depth = 0;
     switch (s->integrator) {
-    case RTG_INTEGRATOR_DIRECT: return direct_only(s, &r, &smp, c);
+    case RTG_INTEGRATOR_DIRECT: L = direct_only(s, &r, &smp, c); break;
     case RTG_INTEGRATOR_ALBEDO: return albedo_only(s, &r, c);
     case RTG_INTEGRATOR_NORMALS: return normals_only(s, &r, c);
-    case RTG_INTEGRATOR_DIRECT_MIS: return direct_mis_only(s, &r, &smp, c);
-    default: return path_trace(s, &r, &thr, 0, &smp, 1, c);
+    case RTG_INTEGRATOR_DIRECT_MIS: L = direct_mis_only(s, &r, &smp, c); break;
+    default: L = path_trace(s, &r, &thr, 0, &smp, 1, c); break;
     }
+    if (smp.max_n) { /* Sobol: the highest draw group n >> 2 any path reached */
+        uint64_t g = (uint64_t)((smp.max_n - 1u) >> 2), old = s->mode_cnt[OR_MODE_SOBOL_MAX_GROUP];
+        while (g > old) {
+            uint64_t seen = __sync_val_compare_and_swap(&s->mode_cnt[OR_MODE_SOBOL_MAX_GROUP], old, g);
+            if (seen == old) break;
+            old = seen;
+        }
+    }
+    return L;
 }
 
 /* ------------------------------------------------------------------ public C API (ctypes) */
@@ -862,12 +1048,14 @@ or_scene* or_create(const rtg_scene_desc* d, int max_depth) {
     memcpy(s->light, d->lights, d->n_lights * sizeof(int));
     s->cs.filter = RTG_FILTER_NONE; s->cs.filter_radius = 0.5f; s->cs.lens_radius = 0.0f; s->cs.focal_distance = 1.0f;
     s->env_cnt = (uint64_t*)calloc(OR_ENV_NCOUNT, sizeof(uint64_t));
+    s->mode_cnt = (uint64_t*)calloc(OR_MODE_NCOUNT, sizeof(uint64_t));
     return s;
 }
 
 void or_destroy(or_scene* s) {
     if (!s) return;
-    free(s->tri); free(s->node); free(s->mat); free(s->tex); free(s->texels); free(s->light); free(s->env_tab); free(s->env_cnt); free(s);
+    free(s->tri); free(s->node); free(s->mat); free(s->tex); free(s->texels); free(s->light); free(s->env_tab); free(s->env_cnt);
+    free(s->light_tab); free(s->grid_tab); free(s->mode_cnt); free(s->cell_seen); free(s);
 }
 
 void or_set_max_depth(or_scene* s, int max_depth) { if (s) s->max_depth = max_depth; }
@@ -914,6 +1102,112 @@ int or_env_counts(or_scene* s, uint64_t* out, int reset) {
     return 0;
 }
 
+/* RTG_LIGHTS_POWER (include/rtg.h): the alias table over the light list that the three pick sites of
+ * computeDirect and computeDirectMIS use, n entries {prob, alias, pmf_self, pmf_alias} as 32-bit words
+ * (copied). The table is an input, as or_set_env_table's is, and any table whose aliases lie inside it is
+ * accepted. n must be the scene's light count. NULL: the uniform pick again, and no grid either. */
+static void drop_grid(or_scene* s) {
+    free(s->grid_tab); free(s->cell_seen);
+    s->grid_tab = NULL; s->cell_seen = NULL;
+    s->grid_dims[0] = s->grid_dims[1] = s->grid_dims[2] = 0;
+}
+int or_set_light_table(or_scene* s, const uint32_t* entries, uint32_t n) {
+    if (!s) return -1;
+    if (!entries) {
+        free(s->light_tab);
+        s->light_tab = NULL;
+        drop_grid(s);
+        return 0;
+    }
+    if (s->nlight <= 0 || n != (uint32_t)s->nlight) return -1;
+    for (uint32_t i = 0; i < n; ++i)
+        if (entries[4 * (size_t)i + 1] >= n) return -1;
+    uint32_t* t = (uint32_t*)malloc((size_t)n * 16);
+    memcpy(t, entries, (size_t)n * 16);
+    free(s->light_tab);
+    s->light_tab = t;
+    return 0;
+}
+
+/* rtg_set_light_grid (include/rtg.h): one table per cell, dims[0] * dims[1] * dims[2] * nlight entries at
+ * table[c * nlight + k], with the kernel's float32 constants lo[3] and scale[3]. It replaces the light
+ * table at the pick sites: the table of a pick is the one of the cell that holds the shading point.
+ * Refused without a light table (the grid refines RTG_LIGHTS_POWER). NULL: off. */
+int or_set_light_grid(or_scene* s, const uint32_t* entries, const uint32_t* dims, const float* lo, const float* scale) {
+    if (!s) return -1;
+    if (!entries) {
+        drop_grid(s);
+        return 0;
+    }
+    if (!s->light_tab || !dims || !lo || !scale) return -1;
+    uint64_t cells = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (dims[a] == 0 || dims[a] > 64) return -1;
+        cells *= dims[a];
+    }
+    uint64_t total = cells * (uint64_t)s->nlight;
+    if (total > (1u << 24)) return -1;
+    for (uint64_t i = 0; i < total; ++i)
+        if (entries[4 * i + 1] >= (uint32_t)s->nlight) return -1;
+    uint32_t* t = (uint32_t*)malloc((size_t)total * 16);
+    memcpy(t, entries, (size_t)total * 16);
+    drop_grid(s);
+    s->grid_tab = t;
+    s->cell_seen = (uint8_t*)calloc((size_t)cells, 1);
+    for (int a = 0; a < 3; ++a) { s->grid_dims[a] = dims[a]; s->grid_lo[a] = lo[a]; s->grid_scale[a] = scale[a]; }
+    return 0;
+}
+
+/* rtg_set_sampler (include/rtg.h): RTG_SAMPLER_SOBOL makes every draw of pixel_sample's path and the four
+ * camera draws Sobol draws; or_render_light and or_render_ir keep PCG. The oracle does what it is told:
+ * the product's fallbacks to PCG are the caller's business. */
+int or_set_sampler(or_scene* s, int sampler) {
+    if (!s || (sampler != RTG_SAMPLER_PCG && sampler != RTG_SAMPLER_SOBOL)) return -1;
+    pthread_once(&g_sb_once, sb_tables);
+    s->sobol = sampler == RTG_SAMPLER_SOBOL;
+    return 0;
+}
+/* Raw Sobol draws first .. first + n - 1 of the stream keyed `key` for sample `sample` (tests: the header's
+ * check values). */
+int or_sobol_draws(uint32_t key, uint32_t sample, uint32_t first, uint32_t n, uint32_t* out) {
+    pthread_once(&g_sb_once, sb_tables);
+    for (uint32_t i = 0; i < n; ++i) out[i] = sb_draw(key, sample, first + i);
+    return 0;
+}
+uint32_t or_sobol_mix32(uint32_t x) { return sb_mix32(x); }
+/* The path stream's (stream 0) or the camera stream's first n raw draws of (pixel, sample) under the
+ * current sampler, without any rounding of the counter: out n. */
+int or_sampler_draws(or_scene* s, uint32_t pixel, uint32_t sample, uint64_t seed, int camera, uint32_t n, uint32_t* out) {
+    if (!s || !out) return -1;
+    Smp q;
+    if (s->sobol) smp_init_sobol(&q, pixel, sample, seed, camera ? 0x9E3779B9u : 0u);
+    else smp_init_pcg(&q, camera ? seed ^ 0x9E3779B97F4A7C15ULL : seed, ((uint64_t)pixel << 16) | sample);
+    for (uint32_t i = 0; i < n; ++i) out[i] = smp_u32(&q);
+    return 0;
+}
+
+/* What the light picks and the Sobol sampler met since the last reset: out[10] = picks from a table, those
+ * that took the alias branch, picks at depth >= 1, NEE samples at depth >= 1 with a non-zero (so visible)
+ * contribution, picks at depth >= 1 whose grid cell is not the cell of the path's camera hit, the number
+ * of distinct cells among those, DIRECT_MIS BSDF-sampled emitter hits under a table, Sobol shading
+ * events at depth >= 1 whose loaded counter was not a multiple of four, those where it was, and the highest
+ * draw group n >> 2 reached. */
+int or_mode_counts(or_scene* s, uint64_t* out, int reset) {
+    if (!s) return -1;
+    uint64_t cells = (uint64_t)s->grid_dims[0] * s->grid_dims[1] * s->grid_dims[2], distinct = 0;
+    if (s->cell_seen)
+        for (uint64_t i = 0; i < cells; ++i) {
+            distinct += s->cell_seen[i];
+            if (reset) s->cell_seen[i] = 0;
+        }
+    s->mode_cnt[OR_MODE_OTHER_CELLS_DISTINCT] = distinct;
+    for (int i = 0; i < OR_MODE_NCOUNT; ++i) {
+        if (out) out[i] = s->mode_cnt[i];
+        if (reset) s->mode_cnt[i] = 0;
+    }
+    return 0;
+}
+
 /* Per-path radiance for an explicit (pixel, sample) list: out n*3. */
 int or_trace_paths(or_scene* s, const uint32_t* pixels, const uint32_t* samples, uint32_t n, uint64_t seed, float* out) {
     if (!s || s->nlight <= 0) return -1;
@@ -927,7 +1221,9 @@ int or_trace_paths(or_scene* s, const uint32_t* pixels, const uint32_t* samples,
 /* Event log of one path (pixel, sample): up to cap events of 5 floats {kind, a, b, c, d}:
  * 1 closest hit {id, t, alpha, beta}, 2 light sample {index, point or direction}, 3 shadow ray
  * {visible, maxT}, 4 Russian roulette {draw, probability, depth}, 5 BSDF sample {wi, pdf}, 6 (after a
- * luminance-mode environment sample's 2) {pdf, accepted}.
+ * luminance-mode environment sample's 2) {pdf, accepted}, 7 light pick from a table {slot k, light, pmf,
+ * grid cell (0 without a grid)}, 8 the opening of a Sobol bounce at depth >= 1 {counter as loaded, counter
+ * after rounding, depth}.
  * Returns the number of events (may exceed cap); radiance goes to L (3 floats). */
 int or_path_events(or_scene* s, uint32_t pixel, uint32_t sample, uint64_t seed, float* ev, int cap, float* L) {
     if (!s || s->nlight <= 0) return -1;
@@ -1163,17 +1459,17 @@ static void connect_to_camera(const struct or_scene* s, V3 p, V3 n, Col c, float
     splat(s, film, k.x, k.y, k.out);
 }
 /* AreaLight: samplePositionFromLight (Triangle::sample) + sampleDirectionFromLight (Lights.h:63-80) */
-static void light_emit_sample(const struct or_scene* s, const Tri* T, Pcg* smp, V3* p, float* pdf_pos, V3* wi,
+static void light_emit_sample(const struct or_scene* s, const Tri* T, Smp* smp, V3* p, float* pdf_pos, V3* wi,
                               float* pdf_dir, V3* gn) {
-    float r1 = pcg_next(smp);
-    float r2 = pcg_next(smp);
+    float r1 = smp_next(smp);
+    float r2 = smp_next(smp);
     float alpha = 1 - sqrtf(r1);
     float beta = r2 * sqrtf(r1);
     float gamma = 1.0f - (alpha + beta);
     *pdf_pos = 1.0f / T->area;
     *p = vadd(vadd(vmuls(T->vx[0].p, alpha), vmuls(T->vx[1].p, beta)), vmuls(T->vx[2].p, gamma));
-    float q2 = pcg_next(smp); /* cosineSampleHemisphere(sampler.next(), sampler.next()) */
-    float q1 = pcg_next(smp);
+    float q2 = smp_next(smp); /* cosineSampleHemisphere(sampler.next(), sampler.next()) */
+    float q1 = smp_next(smp);
     V3 wl = cosine_sample_hemisphere(q1, q2);
     *pdf_dir = (float)((wl.z >= 0.0f) ? (wl.z / O_PI) : 0.0f);
     *gn = vmuls(T->nrm, vdot(T->vx[0].n, T->nrm) > 0 ? 1.0f : -1.0f);
@@ -1182,7 +1478,7 @@ static void light_emit_sample(const struct or_scene* s, const Tri* T, Pcg* smp, 
     (void)s;
 }
 /* RayTracer::lightTracePath (Renderer.h:292-326) */
-static void light_trace_path(const struct or_scene* s, Ray* r, Col thr, Col Le, Pcg* smp, float* film, LightCounts* c) {
+static void light_trace_path(const struct or_scene* s, Ray* r, Col thr, Col Le, Smp* smp, float* film, LightCounts* c) {
     for (;;) {
         Isect is = scene_traverse(s, r, c ? &c->c : NULL);
         Shading sd = shading_data(s, &is, r);
@@ -1192,7 +1488,7 @@ static void light_trace_path(const struct or_scene* s, Ray* r, Col thr, Col Le, 
         Col cl = cmul(cmul(thr, bsdf_eval(s, &sd)), Le);
         connect_to_camera(s, sd.x, sd.sN, cl, film, c);
         float rrp = win_min(clum(thr), 0.9f);
-        if (pcg_next(smp) < rrp) thr = cdivs(thr, rrp);
+        if (smp_next(smp) < rrp) thr = cdivs(thr, rrp);
         else return;
         Col ind;
         float pdf;
@@ -1221,10 +1517,10 @@ int or_render_light(or_scene* s, uint32_t first, uint32_t n_frames, uint64_t see
     for (uint32_t f = first; f < first + n_frames; ++f) {
         for (uint32_t i = 0; i < (uint32_t)(s->W * s->H); ++i) {
             if (counts) counts[LP_PATHS]++;
-            Pcg smp;
-            pcg_init(&smp, seed, ((uint64_t)i << 16) | f);
+            Smp smp; /* (the light paths keep PCG whatever or_set_sampler says) */
+            smp_init_pcg(&smp, seed, ((uint64_t)i << 16) | f);
             float pmf = 1.f / (float)s->nlight;
-            int li = (int)((float)s->nlight * pcg_next(&smp));
+            int li = (int)((float)s->nlight * smp_next(&smp));
             if (s->nlight - 1 < li) li = s->nlight - 1;
             int lt = s->light[li];
             if (lt < 0) continue; /* light->isArea() */
@@ -1257,7 +1553,7 @@ static void vpl_push(VplList* l, V3 x, V3 n, Col Le) {
     l->n++;
 }
 /* RayTracer::VPLTracePath (Renderer.h:183-218, recursion unrolled) */
-static void vpl_trace_path(const struct or_scene* s, Ray* r, Col thr, Col Le, Pcg* smp, VplList* out, Counts* c) {
+static void vpl_trace_path(const struct or_scene* s, Ray* r, Col thr, Col Le, Smp* smp, VplList* out, Counts* c) {
     for (;;) {
         Isect is = scene_traverse(s, r, c);
         Shading sd = shading_data(s, &is, r);
@@ -1265,7 +1561,7 @@ static void vpl_trace_path(const struct or_scene* s, Ray* r, Col thr, Col Le, Pc
         if (!is_light(sd.bsdf) && !is_spec(sd.bsdf))
             vpl_push(out, sd.x, sd.sN, cmuls(cmul(cmul(thr, Le), bsdf_eval(s, &sd)), fabsf(vdot(vneg(r->dir), sd.sN))));
         float rrp = win_min(clum(thr), 0.9f);
-        if (pcg_next(smp) < rrp) thr = cdivs(thr, rrp);
+        if (smp_next(smp) < rrp) thr = cdivs(thr, rrp);
         else return;
         Col val;
         float pdf;
@@ -1287,10 +1583,10 @@ int or_render_ir(or_scene* s, uint32_t first, uint32_t n_frames, uint64_t seed, 
         VplList vl = {NULL, 0, 0};
         if (counts) counts[LP_PATHS] += (uint64_t)n_vpl + (uint64_t)s->W * (uint64_t)s->H;
         for (uint32_t i = 0; i < n_vpl; ++i) {
-            Pcg smp;
-            pcg_init(&smp, seed, ((uint64_t)i << 16) | f);
+            Smp smp; /* (the light paths keep PCG whatever or_set_sampler says) */
+            smp_init_pcg(&smp, seed, ((uint64_t)i << 16) | f);
             float pmf = 1.f / (float)s->nlight;
-            int li = (int)((float)s->nlight * pcg_next(&smp));
+            int li = (int)((float)s->nlight * smp_next(&smp));
             if (s->nlight - 1 < li) li = s->nlight - 1;
             int lt = s->light[li];
             if (lt < 0) continue;

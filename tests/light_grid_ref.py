@@ -125,6 +125,101 @@ def build(records, weights, root_box, cells, lam):
     return {"dims": dims, "lo": lo, "scale": scale, "weights": wc, "pmf": pmf, "entries": ent, "uniform": unif}
 
 
+def _vose_lockstep(p, positive):
+    """light_sampling_ref.vose on every row of p (cells, n) at once: the same stacks, pops and pushes per
+    row, the rows advancing together (a row whose stacks ran out waits). Returns (prob float64, alias)."""
+    nc, n = p.shape
+    p = p.copy()
+    prob = np.ones((nc, n), np.float64)
+    alias = np.tile(np.arange(n, dtype=np.int64), (nc, 1))
+    is_small = p < 1.0
+    # stacks as index arrays filled from the left in increasing index order, and their sizes
+    order = np.argsort(~is_small, axis=1, kind="stable")   # the small indices first, increasing
+    small, n_small = order.copy(), is_small.sum(1)
+    order = np.argsort(is_small, axis=1, kind="stable")    # the large indices first, increasing
+    large, n_large = order.copy(), n - n_small
+    for _ in range(n):
+        act = np.flatnonzero((n_small > 0) & (n_large > 0))
+        if not len(act):
+            break
+        s = small[act, n_small[act] - 1]
+        l = large[act, n_large[act] - 1]
+        n_small[act] -= 1
+        n_large[act] -= 1
+        prob[act, s] = p[act, s]
+        alias[act, s] = l
+        p[act, l] = (p[act, l] + p[act, s]) - 1.0
+        to_small = p[act, l] < 1.0
+        a, b = act[to_small], act[~to_small]
+        small[a, n_small[a]] = l[to_small]
+        n_small[a] += 1
+        large[b, n_large[b]] = l[~to_small]
+        n_large[b] += 1
+    left = np.arange(n)[None, :] < n_small[:, None]          # what stayed on the small stacks
+    r, k = np.nonzero(left)
+    idx = small[r, k]
+    prob[r, idx] = np.where(positive[r, idx], 1.0, 0.0)
+    return prob, alias.astype(U32)
+
+
+def build_fast(records, weights, root_box, cells, lam):
+    """build()'s "dims", "lo", "scale" and "entries", computed for a slab of z layers of cells at once, for grids
+    whose cells a Python loop would take minutes over (64 x 64 x 64). The same binary64 operations in the
+    same order per cell; tests/test_light_grid.py holds it equal to build() bit for bit."""
+    dims, lo32, scale = layout(root_box, cells)
+    rec = np.asarray(records, F).reshape(-1, 20)
+    w = np.asarray(weights, np.float64).reshape(-1)
+    n = len(w)
+    rb = np.asarray(root_box, F).reshape(-1)[:6].astype(np.float64)
+    lo, e = rb[:3], rb[3:6] - rb[:3]
+    s = e / np.asarray(dims, np.float64)
+    r2 = 0.25 * ((s[0] * s[0] + s[1] * s[1]) + s[2] * s[2])
+    R = 0.5 * math.sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2])
+    kind = rec[:, 7].copy().view(np.int32)
+    v = rec[:, [0, 1, 2, 4, 5, 6, 8, 9, 10]].astype(np.float64).reshape(-1, 3, 3)
+    tlo, thi = v.min(1), v.max(1)
+    v0, gn = rec[:, 0:3].astype(np.float64), rec[:, 12:15].astype(np.float64)
+    lam = float(lam)
+    dx, dy, dz = (int(d) for d in dims)
+    ent = np.zeros((dx * dy * dz, n, 4), U32)
+    nz = max(1, 4096 // (dx * dy))  # z layers per slab (larger slabs fall out of the cache and run slower)
+    uni = uniform_entries(n)
+    with np.errstate(all="ignore"):
+        for z0 in range(0, dz, nz):
+            iz, iy, ix = (a.reshape(-1).astype(np.float64) for a in
+                          np.meshgrid(np.arange(z0, min(z0 + nz, dz)), np.arange(dy), np.arange(dx), indexing="ij"))
+            ii = np.stack([ix, iy, iz], axis=1)                                   # (c, 3), x fastest
+            clo, chi = lo + ii * s, lo + (ii + 1.0) * s
+            d = np.maximum(np.maximum(0.0, tlo[None] - chi[:, None]), clo[:, None] - thi[None])  # (c, n, 3)
+            d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+            g = 1.0 / np.maximum(d2, r2)
+            faces = np.zeros(g.shape, bool)
+            for k in range(8):
+                kx = chi[:, 0] + s[0] / 2.0 if k & 1 else clo[:, 0] - s[0] / 2.0
+                ky = chi[:, 1] + s[1] / 2.0 if k & 2 else clo[:, 1] - s[1] / 2.0
+                kz = chi[:, 2] + s[2] / 2.0 if k & 4 else clo[:, 2] - s[2] / 2.0
+                dt = (((kx[:, None] - v0[None, :, 0]) * gn[None, :, 0] + (ky[:, None] - v0[None, :, 1]) * gn[None, :, 1])
+                      + (kz[:, None] - v0[None, :, 2]) * gn[None, :, 2])
+                faces |= dt > 0.0
+            g = np.where(faces, g, 0.0)
+            g = np.where(kind[None] == 0, g, 1.0 / (R * R))
+            wc = w[None] * g                                                       # (c, n)
+            total = np.cumsum(wc, axis=1)[:, -1]
+            ok = np.isfinite(wc).all(1) & (total > 0.0) & np.isfinite(total)
+            pmf = ((1.0 - lam) * wc) / total[:, None] + lam / float(n)
+            pmf = np.where(ok[:, None], pmf, 1.0)
+            prob, alias = _vose_lockstep(pmf * float(n), pmf > 0)
+            pf = pmf.astype(F)
+            slab = np.zeros((len(ix), n, 4), U32)
+            slab[..., 0] = prob.astype(F).view(U32)
+            slab[..., 1] = alias
+            slab[..., 2] = pf.view(U32)
+            slab[..., 3] = np.take_along_axis(pf, alias.astype(np.int64), axis=1).view(U32)
+            slab[~ok] = uni
+            ent[z0 * dx * dy:z0 * dx * dy + len(ix)] = slab
+    return {"dims": dims, "lo": lo32, "scale": scale, "entries": ent}
+
+
 def pick(entries, cell, r0, d1):
     """light_pick against the table of each point's cell: (li (n,) int64, pmf (n,) float32)."""
     ent = np.asarray(entries, U32)

@@ -32,6 +32,10 @@ int or_render(or_scene* s, uint32_t first, uint32_t n_samples, uint64_t seed, co
               int threads, float* film, uint64_t* counts, int count);
 int or_set_camera_sampling(or_scene* s, int filter, float filter_radius, float lens_radius, float focal_distance);
 int or_set_env_table(or_scene* s, const uint32_t* entries, uint32_t W, uint32_t H);
+int or_set_light_table(or_scene* s, const uint32_t* entries, uint32_t n);
+int or_set_light_grid(or_scene* s, const uint32_t* entries, const uint32_t* dims, const float* lo, const float* scale);
+int or_set_sampler(or_scene* s, int sampler);
+int or_mode_counts(or_scene* s, uint64_t* out, int reset);
 int or_render_light(or_scene* s, uint32_t first, uint32_t n_frames, uint64_t seed, float* film, uint64_t* counts);
 int or_render_ir(or_scene* s, uint32_t first, uint32_t n_frames, uint64_t seed, uint32_t n_vpl, float* film,
                  uint64_t* counts);
@@ -184,6 +188,39 @@ void load_and_render(const std::string& dir, int width, int height, bool render,
             std::vector<float> film((size_t)info.width * info.height * 3, 0.0f);
             uint64_t counts[5] = {0, 0, 0, 0, 0};
             if (or_render(os, 0, 1, 1234, nullptr, 0, 1, film.data(), counts, 1) != 0) g_fail = 1;
+            {
+                // the light pick, the light grid and the Sobol sampler: a table whose even entries keep their
+                // light and whose odd ones defer to the last, the same table in each of 2 x 1 x 3 cells; the
+                // argument errors first (a wrong n, a grid without a table, an alias past the table)
+                const uint32_t n = d->n_lights;
+                const float one = 1.0f, pm = 1.0f / (float)n;
+                std::vector<uint32_t> tab((size_t)6 * n * 4);
+                for (uint32_t k = 0; k < 6 * n; ++k) {
+                    std::memcpy(&tab[4 * (size_t)k], &one, 4);
+                    if (k & 1) tab[4 * (size_t)k] = 0;
+                    tab[4 * (size_t)k + 1] = (k & 1) ? n - 1 : k % n;
+                    std::memcpy(&tab[4 * (size_t)k + 2], &pm, 4);
+                    std::memcpy(&tab[4 * (size_t)k + 3], &pm, 4);
+                }
+                const uint32_t dims[3] = {2, 1, 3}, zero_dims[3] = {2, 0, 3};
+                const float lo[3] = {-1.0f, 0.0f, -1.0f}, scale[3] = {1.0f, 0.0f, 1.5f};
+                if (or_set_light_table(os, tab.data(), n + 1) == 0) g_fail = 1;
+                if (or_set_light_grid(os, tab.data(), dims, lo, scale) == 0) g_fail = 1;
+                if (or_set_sampler(os, 2) == 0) g_fail = 1;
+                std::vector<uint32_t> bad(tab.begin(), tab.begin() + (size_t)n * 4);
+                bad[1] = n;
+                if (or_set_light_table(os, bad.data(), n) == 0) g_fail = 1;
+                if (or_set_light_table(os, tab.data(), n) != 0) g_fail = 1;
+                if (or_set_light_grid(os, tab.data(), zero_dims, lo, scale) == 0) g_fail = 1;
+                if (or_set_light_grid(os, tab.data(), dims, lo, scale) != 0) g_fail = 1;
+                if (or_set_sampler(os, 1) != 0) g_fail = 1;
+                if (or_render(os, 2, 1, 1234, nullptr, 0, 2, film.data(), counts, 1) != 0) g_fail = 1;
+                uint64_t mc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                if (or_mode_counts(os, mc, 1) != 0 || mc[0] == 0) g_fail = 1;
+                if (or_set_sampler(os, 0) != 0) g_fail = 1;
+                if (or_set_light_grid(os, nullptr, nullptr, nullptr, nullptr) != 0) g_fail = 1;
+                if (or_set_light_table(os, nullptr, 0) != 0) g_fail = 1;
+            }
             if (d->env_texture >= 0) {
                 // the oracle's opt-in sampling modes: tent + lens, and an alias table over the map's cells
                 // whose even entries keep their cell and whose odd ones defer to the last cell

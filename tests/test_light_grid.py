@@ -187,6 +187,29 @@ def test_an_all_zero_cell_is_uniform():
         assert (ent[3, :, 2].copy().view(F) == F(1.0 / 3.0)).all()
 
 
+@pytest.mark.parametrize("name,cells,env", [("hall32", 8, False), ("room", 5, False), ("hall12", 5, True)])
+def test_slab_wise_restatement_equals_the_cell_wise_one(tmp_path, name, cells, env):
+    """light_grid_ref.build_fast (a z slab of cells at once, Vose in lockstep; the whole-film GPU tests use it
+    at 64 cells) gives build()'s layout and entries bit for bit, at lambda 0 and 0.125, and on
+    test_an_all_zero_cell_is_uniform's box, where one cell takes the uniform table."""
+    rec, w, rb = scene_case(tmp_path, name)
+    if env:
+        rec, w = with_environment(rec, w)
+    for lam in (0.0, LAM):
+        a, b = gr.build(rec, w, rb, cells, lam), gr.build_fast(rec, w, rb, cells, lam)
+        assert np.array_equal(a["dims"], b["dims"]) and np.array_equal(a["lo"].view(np.uint32), b["lo"].view(np.uint32))
+        assert np.array_equal(a["scale"].view(np.uint32), b["scale"].view(np.uint32))
+        assert np.array_equal(a["entries"], b["entries"]), (name, lam, int((a["entries"] != b["entries"]).any(2).sum()))
+    rec3 = np.zeros((3, 20), F)
+    for k in range(3):
+        rec3[k, 0:3], rec3[k, 4:7], rec3[k, 8:11] = (2.0, 0.2 + 0.1 * k, 0.4), (2.0, 0.6, 0.4), (2.0, 0.4, 0.6)
+        rec3[k, 3], rec3[k, 11], rec3[k, 12] = 0.02, 50.0, -1.0
+        rec3[k, 16:19] = (1.0 + k, 1.0, 1.0)
+    box = np.array([0, 0, 0, 4, 1, 1], F)
+    a, b = gr.build(rec3, lr.light_weights(rec3), box, 4, 0.0), gr.build_fast(rec3, lr.light_weights(rec3), box, 4, 0.0)
+    assert a["uniform"].any() and np.array_equal(a["entries"], b["entries"])
+
+
 def test_restated_cell_of_a_point():
     """Faces, the outside, NaN and infinities, on a grid with a degenerate axis."""
     dims, lo, sc = gr.layout(np.array([-8, 0, -1, 8, 0, 1], F), 8)

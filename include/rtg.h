@@ -939,7 +939,8 @@ int  rtg_temporal_ms(rtg_handle* h, double* guide_ms, double* accumulate_ms);
  * wait in between; the call returns when the result is in the handle's device buffer, and in out when given.
  * rtg_svgf_ms gives the device time of the last call's guide pass (0 when none ran), temporal + moments
  * kernel, variance kernel and all filter levels together (the copy of the positions included). Not covered:
- * albedo demodulation, feeding level 0's output back into the history, groups, the CLI, integration/rtg_rtbase.h, reprojecting the background, moving geometry. */
+ * feeding level 0's output back into the history, groups, integration/rtg_rtbase.h, reprojecting the background,
+ * moving geometry. Albedo demodulation is rtg_svgf_illum_accumulate, below. */
 typedef struct rtg_svgf_params {
     rtg_temporal_params temporal;   /* max_history, plane_tolerance, normal_cos: as rtg_temporal_accumulate */
     uint32_t iterations;            /* 1..RTG_DENOISE_MAX_ITERATIONS, default 5 */
@@ -956,6 +957,54 @@ int  rtg_svgf_variance(rtg_handle* h, float* var /* w*h */);
 int  rtg_svgf_moments(rtg_handle* h, float* mu /* w*h*2 */);
 int  rtg_svgf_copy_device(rtg_handle* h, void* dst_device);
 int  rtg_svgf_ms(rtg_handle* h, double* guide_ms, double* accumulate_ms, double* variance_ms, double* filter_ms);
+
+/* ---- the illumination mode of the variance-guided chain (rtg_svgf_illum.hip,
+ * tests/svgf_illum_ref.py restates it in numpy): rtg_svgf_accumulate's chain run on the film over the first
+ * hit's albedo, with the pixels that see an emitter directly kept in a class of their own. Opt-in: nothing
+ * changes unless these calls are made. IEEE float32 with one rounding per operation, no contraction.
+ *   inputs      A, the denoiser's albedo guide of the current camera (the `0 + c` image rtg_gbuffer writes), and G,
+ *               its geometry guide.
+ *   divisor     per channel d.c = A.c > albedo_floor ? A.c : 1.0f (a NaN fails the comparison and gives 1).
+ *   classed G'  G, except that a pixel whose first-hit material is a light (L(emission) > 0, the test rtg_gbuffer
+ *               makes first) gets the miss records {0, 0, 0, FLT_MAX} {0, 0, 0, id = -1}.
+ *   prepare     F'[p].c = film[p].c / d.c: the film's sums, so cur = F' / m follows unchanged.
+ *   chain       rtg_svgf_accumulate's steps 1-3, word for word, on F' and G': the temporal step reprojects with
+ *               G', the stored history guide is G', the variance window and the filter's plane test use G'. The
+ *               albedo and shading-normal terms read the denoiser's guide as it is (an emitter against the
+ *               background still gets weight 0 from the normal term). An emitter pixel therefore restarts every
+ *               frame (len = m) and exchanges nothing with surfaces.
+ *   remodulate  out.c = rgb.c d.c on the last level's record.
+ * State: the mode keeps a history H' (illumination and len), moments, history camera and history guide (G') of
+ * its own. rtg_svgf_accumulate's and rtg_temporal_accumulate's H and M are not touched by it and do not touch
+ * its: rtg_temporal_history returns what the default-mode calls alone left. rtg_temporal_reset drops both. The
+ * guide caches stay unclassed: rtg_geometry_guide, rtg_gbuffer, rtg_temporal_accumulate and rtg_svgf_accumulate
+ * return the same bits before and after illumination calls. The film, Film::SPP, the integrator, the options and
+ * the statistics are left as they were; a failed call leaves both states and the film as they were.
+ * albedo_floor must be finite and > 0 and svgf as rtg_svgf_check says; anything else is RTG_ERR_ARG before any
+ * device call (rtg_svgf_illum_check is that check alone). The default floor 1e-3 is a stated choice, not an
+ * optimum. The whole chain (the first-hit pass if a guide is missing, k_svgf_illum_prepare, rtg_svgf_accumulate's
+ * kernels, k_svgf_illum_unpack) is queued on the handle's stream and waited for once.
+ * Read-backs (RTG_ERR_ARG before the first illumination call): rtg_svgf_illum_history H' (w*h*4),
+ * rtg_svgf_illum_variance step 2's v (w*h), rtg_svgf_illum_moments (w*h*2), rtg_svgf_illum_guide the classed
+ * guide of the history camera (two w*h*4 images, either may be NULL), rtg_svgf_illum_copy_device the last result;
+ * rtg_svgf_illum_ms rtg_svgf_ms's four times plus the device time of the prepare and of the unpack kernel.
+ * Not covered: rtg_temporal_accumulate, which has the same bleed of a directly seen emitter into the surface
+ * next to it; groups; feeding level 0 back into the history; integration/rtg_rtbase.h; a measured gain from
+ * demodulation on high-frequency textures (none of this repository's scenes shows one). */
+typedef struct rtg_svgf_illum_params {
+    rtg_svgf_params svgf;           /* as rtg_svgf_accumulate */
+    float albedo_floor;             /* > 0 finite, default 1e-3: channels at or below it are not divided */
+} rtg_svgf_illum_params;
+int  rtg_svgf_illum_defaults(rtg_svgf_illum_params* p);  /* rtg_svgf_defaults; 1e-3f */
+int  rtg_svgf_illum_check(const rtg_svgf_illum_params* p);
+int  rtg_svgf_illum_accumulate(rtg_handle* h, const rtg_svgf_illum_params* p, float* out /* w*h*3 or NULL */);
+int  rtg_svgf_illum_history(rtg_handle* h, float* rgb_len /* w*h*4 */);
+int  rtg_svgf_illum_variance(rtg_handle* h, float* var /* w*h */);
+int  rtg_svgf_illum_moments(rtg_handle* h, float* mu /* w*h*2 */);
+int  rtg_svgf_illum_guide(rtg_handle* h, float* pos_t /* w*h*4 */, float* normal_id /* w*h*4 */);
+int  rtg_svgf_illum_copy_device(rtg_handle* h, void* dst_device);
+int  rtg_svgf_illum_ms(rtg_handle* h, double* guide_ms, double* accumulate_ms, double* variance_ms,
+                       double* filter_ms, double* prepare_ms, double* unpack_ms);
 
 /* ---- the G-buffer: one first-hit pass for the geometry guide and the albedo / shading-normal guides (DESIGN.md
  * §8k; rtg_gbuffer.hip). The pinhole ray through every pixel centre (whatever rtg_set_camera_sampling says) is

@@ -107,6 +107,10 @@ class rtg_svgf_params(C.Structure):
                 ("variance_floor", C.c_float)]
 
 
+class rtg_svgf_illum_params(C.Structure):
+    _fields_ = [("svgf", rtg_svgf_params), ("albedo_floor", C.c_float)]
+
+
 class rth_load_options(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("skip_missing", C.c_int32),
                 ("bvh_threads", C.c_int32), ("envmap", C.c_char_p)]
@@ -263,6 +267,16 @@ RTG_EXPORTS = [
     ("rtg_svgf_moments", C.c_int, [C.c_void_p, f32p]),
     ("rtg_svgf_copy_device", C.c_int, [C.c_void_p, C.c_void_p]),
     ("rtg_svgf_ms", C.c_int, [C.c_void_p] + [C.POINTER(C.c_double)] * 4),
+    # ... its illumination mode (rtg_svgf_illum.hip)
+    ("rtg_svgf_illum_defaults", C.c_int, [C.POINTER(rtg_svgf_illum_params)]),
+    ("rtg_svgf_illum_check", C.c_int, [C.POINTER(rtg_svgf_illum_params)]),
+    ("rtg_svgf_illum_accumulate", C.c_int, [C.c_void_p, C.POINTER(rtg_svgf_illum_params), f32p]),
+    ("rtg_svgf_illum_history", C.c_int, [C.c_void_p, f32p]),
+    ("rtg_svgf_illum_variance", C.c_int, [C.c_void_p, f32p]),
+    ("rtg_svgf_illum_moments", C.c_int, [C.c_void_p, f32p]),
+    ("rtg_svgf_illum_guide", C.c_int, [C.c_void_p, f32p, f32p]),
+    ("rtg_svgf_illum_copy_device", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("rtg_svgf_illum_ms", C.c_int, [C.c_void_p] + [C.POINTER(C.c_double)] * 6),
     # the fused first-hit pass (rtg_gbuffer.hip)
     ("rtg_gbuffer", C.c_int, [C.c_void_p, f32p, f32p, f32p, f32p]),
     ("rtg_gbuffer_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),

@@ -33,7 +33,7 @@ DEVICE_SRC = ["device/rtg_trace.hip", "device/rtg_scene.hip", "device/rtg_render
               "device/rtg_denoise.hip", "device/rtg_env.hip", "device/rtg_light_pick.hip",
               "device/rtg_shade_phys.hip", "device/rtg_shade_mis.hip", "device/rtg_shade_trans.hip",
               "device/rtg_temporal.hip", "device/rtg_svgf.hip", "device/rtg_gbuffer.hip",
-              "device/rtg_light_grid.hip"]
+              "device/rtg_light_grid.hip", "device/rtg_svgf_illum.hip"]
 # per-unit compile flags: k_shade's translation unit takes LLVM's max-ilp scheduler, which its
 # latency-bound body prefers, while the traversal keeps the default; the traversal's
 # unit is built without SLP vectorisation, whose packed FP32 pairs in the triangle test held k_trace at

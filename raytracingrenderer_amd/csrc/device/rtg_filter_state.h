@@ -1,6 +1,6 @@
 // rtg_filter_state.h — the host layer shared by the film-filter units: the denoiser (rtg_denoise.hip), the
-// temporal unit (rtg_temporal.hip), the variance-guided chain that joins them (rtg_svgf.hip) and the fused
-// first-hit pass that feeds them (rtg_gbuffer.hip). Their states own their device memory (DevBuf) and their
+// temporal unit (rtg_temporal.hip), the variance-guided chain that joins them (rtg_svgf.hip), its illumination
+// mode (rtg_svgf_illum.hip) and the fused first-hit pass that feeds them (rtg_gbuffer.hip). Their states own their device memory (DevBuf) and their
 // timing events (DevEvents), so releasing one is `delete`; each is built as a local object and handed to the
 // handle only once every allocation has succeeded, so the handle never holds a half-built
 // one. No kernel and no device function lives here: the two temporal kernels share rtg_reproject.h, every
@@ -30,20 +30,35 @@ struct SvgfState {  // rtg_svgf.hip's part of the temporal state
     double guide_ms = 0.0, accumulate_ms = 0.0, variance_ms = 0.0, filter_ms = 0.0;
 };
 
-struct TemporalState {
-    size_t n = 0;                           // pixels the buffers hold
+struct HistoryTrack {  // a history with the camera it was seen from and that camera's guide
     DevBuf<float4> hist[2];                 // hist[cur] is H
     int cur = 0;
     DevBuf<float4> hguide;                  // the history camera's guide (valid when have_hist)
+    bool have_hist = false;
+    DevCamera hcam{};
+    rtg_camera_proj hproj{};
+};
+
+struct SvgfIllumState {  // rtg_svgf_illum.hip's part: the illumination mode's own history, moments and guide
+    HistoryTrack k;                         // H' (illumination), its camera and its classed guide
+    SvgfState sv;                           // M', the filter's buffers, the last result
+    DevBuf<float> film;                     // F', the film's sums over the divisor
+    DevBuf<float4> guide;                   // G', the current camera's classed guide (swapped with k.hguide)
+    double prepare_ms = 0.0, unpack_ms = 0.0;
+};
+
+struct TemporalState : HistoryTrack {
+    size_t n = 0;                           // pixels the buffers hold
     DevBuf<float4> cguide;                  // the guide cache (valid for ccam / cproj when cache_ready)
     DevBuf<float> out;                      // last result, tightly packed rgb
-    bool have_hist = false, cache_ready = false, have_result = false;
-    DevCamera hcam{}, ccam{};
-    rtg_camera_proj hproj{}, cproj{};
+    bool cache_ready = false, have_result = false;
+    DevCamera ccam{};
+    rtg_camera_proj cproj{};
     DevEvents<4> ev;
     double guide_ms = 0.0, accumulate_ms = 0.0;
     double gbuffer_ms = 0.0;                // the fused pass of the last rtg_gbuffer / rtg_svgf_accumulate (0: none ran)
     std::unique_ptr<SvgfState> sv;          // built by the first rtg_svgf_accumulate
+    std::unique_ptr<SvgfIllumState> il;     // built by the first rtg_svgf_illum_accumulate
 };
 
 struct DenoiseState {
@@ -88,6 +103,19 @@ int copy_result(const char* who, rtg_handle* h, const float* result, void* dst_d
 int denoise_state(rtg_handle* h);
 // the albedo / shading-normal guides, rendered and packed when dropped; wait: the host waits for them
 int ensure_guides(rtg_handle* h, bool wait = true);
+// rtg_svgf.hip
+// RTG_ERR_ARG (with "who: ..." as the message) for parameters outside include/rtg.h's ranges
+int svgf_check(const char* who, const rtg_svgf_params* p);
+// the buffers and events of a variance-guided state for n pixels
+int svgf_alloc(SvgfState& s, size_t n);
+// One step of the chain queued on h's stream with no host wait: k_svgf_temporal on `film` over the history k and
+// the moments of s, k_svgf_variance, the copy of the positions and the levels, with g the current camera's
+// geometry guide (k's own when the camera is k's: *unchanged). Records s.ev[2..5]; the last level's records are
+// s.col[p->iterations & 1]. Nothing of k or s is advanced: svgf_done does that once the stream has been waited for.
+int svgf_queue(rtg_handle* h, const rtg_svgf_params* p, const HistoryTrack& k, SvgfState& s, const float* film,
+               const float4* g, bool* unchanged);
+// after the wait: the stage times (the guide pass ran: traced), M flips and the state holds a result
+void svgf_done(SvgfState& s, bool traced);
 // rtg_gbuffer.hip: k_gbuffer on st, from the first hits in pb into geo (2 records per pixel) and d's three
 // guide buffers
 int launch_gbuffer(rtg_handle* h, const PathBufs& pb, float4* geo, DenoiseState& d, hipStream_t st);
@@ -96,7 +124,7 @@ int launch_gbuffer(rtg_handle* h, const PathBufs& pb, float4* geo, DenoiseState&
 // (returned), the mode that follows, and every field the two kernels share but gcur, which the caller sets in
 // mode 2 once it has the current guide.
 template <class Args>
-static inline bool temporal_setup(const rtg_handle* h, const TemporalState& t, const rtg_temporal_params& p, Args& a) {
+static inline bool temporal_setup(const rtg_handle* h, const HistoryTrack& t, const rtg_temporal_params& p, Args& a) {
     const bool unchanged = t.have_hist && same_camera(h->cam, h->proj, t.hcam, t.hproj);
     a.film = h->d_film;
     a.m = (float)h->spp;

@@ -304,23 +304,27 @@ __global__ __launch_bounds__(256) void k_svgf_unpack(const float4* __restrict__ 
 }
 
 // ------------------------------------------------------------------ host side
+int svgf_alloc(SvgfState& s, size_t n) {
+    if (int rc = s.ev.create()) return rc;
+    for (DevBuf<float2>& b : s.mom)
+        if (int rc = b.alloc(n)) return rc;
+    for (DevBuf<float4>* b : {&s.col[0], &s.col[1], &s.xpos})
+        if (int rc = b->alloc(n)) return rc;
+    if (int rc = s.var.alloc(n)) return rc;
+    return s.out.alloc(3 * n);
+}
+
 // The temporal state's variance-guided part, built on first use: a local one, handed to t by the last statement
 // (a failed allocation leaves t.sv null and the next call builds again). t's destructor frees it.
 static int build_state(TemporalState& t) {
     if (t.sv) return RTG_OK;
     auto s = std::make_unique<SvgfState>();
-    if (int rc = s->ev.create()) return rc;
-    for (DevBuf<float2>& b : s->mom)
-        if (int rc = b.alloc(t.n)) return rc;
-    for (DevBuf<float4>* b : {&s->col[0], &s->col[1], &s->xpos})
-        if (int rc = b->alloc(t.n)) return rc;
-    if (int rc = s->var.alloc(t.n)) return rc;
-    if (int rc = s->out.alloc(3 * t.n)) return rc;
+    if (int rc = svgf_alloc(*s, t.n)) return rc;
     t.sv = std::move(s);
     return RTG_OK;
 }
 
-static int svgf_check(const char* who, const rtg_svgf_params* p) {
+int svgf_check(const char* who, const rtg_svgf_params* p) {
     auto bad = [&](const char* what) {
         g_err = std::string(who) + ": " + what;
         return RTG_ERR_ARG;
@@ -335,6 +339,74 @@ static int svgf_check(const char* who, const rtg_svgf_params* p) {
     if (!(std::isfinite(p->min_history) && p->min_history > 0.0f)) return bad("min_history must be finite and > 0");
     if (!(std::isfinite(p->variance_floor) && p->variance_floor > 0.0f)) return bad("variance_floor must be finite and > 0");
     return RTG_OK;
+}
+
+int svgf_queue(rtg_handle* h, const rtg_svgf_params* p, const HistoryTrack& k, SvgfState& s, const float* film,
+               const float4* g, bool* unchanged) {
+    hipStream_t st = h->stream;
+    const size_t n = (size_t)h->W * h->H;
+    const dim3 grid((unsigned)(h->W + 63) / 64, (unsigned)(h->H + 3) / 4);
+    SvgfTemporalArgs a{};
+    *unchanged = temporal_setup(h, k, p->temporal, a);
+    a.film = film;
+    a.mom_on = (k.have_hist && s.mom_valid) ? 1 : 0;
+    a.mom_in = s.mom[s.cur].p;
+    a.mom_out = s.mom[s.cur ^ 1].p;
+    if (a.mode == 2) a.gcur = g;
+    HIPOK(hipEventRecord(s.ev[2], st));
+    hipLaunchKernelGGL(k_svgf_temporal, grid, dim3(256), 0, st, a);
+    LAUNCH_OK("k_svgf_temporal");
+    HIPOK(hipEventRecord(s.ev[3], st));
+
+    SvgfVarianceArgs v{};
+    v.hist = a.hout;
+    v.mom = a.mom_out;
+    v.geo = g;
+    v.col = s.col[0].p;
+    v.var = s.var.p;
+    v.W = h->W;
+    v.H = h->H;
+    v.min_history = p->min_history;
+    v.plane_tolerance = p->temporal.plane_tolerance;
+    v.normal_cos = p->temporal.normal_cos;
+    hipLaunchKernelGGL(k_svgf_variance, grid, dim3(256), 0, st, v);
+    LAUNCH_OK("k_svgf_variance");
+    HIPOK(hipEventRecord(s.ev[4], st));
+
+    hipLaunchKernelGGL(k_svgf_pack_pos, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, n, s.xpos.p);
+    LAUNCH_OK("k_svgf_pack_pos");
+    SvgfFilterArgs f{};
+    f.guide = h->dn->guide.p;
+    f.geo = g;
+    f.xpos = s.xpos.p;
+    f.W = h->W;
+    f.H = h->H;
+    f.m = (int)p->normal_squarings;
+    f.alb_on = p->sigma_albedo > 0.0f;
+    f.s2 = p->sigma_luminance * p->sigma_luminance;
+    f.floor = p->variance_floor;
+    f.ia = f.alb_on ? 1.0f / (p->sigma_albedo * p->sigma_albedo) : 0.0f;
+    f.plane_tolerance = p->temporal.plane_tolerance;
+    for (uint32_t i = 0; i < p->iterations; ++i) {
+        f.cin = s.col[i & 1].p;
+        f.cout = s.col[(i + 1) & 1].p;
+        f.step = 1 << i;
+        hipLaunchKernelGGL(k_svgf_atrous, grid, dim3(256), 0, st, f);
+        LAUNCH_OK("k_svgf_atrous");
+    }
+    HIPOK(hipEventRecord(s.ev[5], st));
+    return RTG_OK;
+}
+
+void svgf_done(SvgfState& s, bool traced) {
+    float ms = 0.0f;
+    s.guide_ms = stage_ms(traced, s.ev[0], s.ev[1]);
+    if (hipEventElapsedTime(&ms, s.ev[2], s.ev[3]) == hipSuccess) s.accumulate_ms = ms;
+    if (hipEventElapsedTime(&ms, s.ev[3], s.ev[4]) == hipSuccess) s.variance_ms = ms;
+    if (hipEventElapsedTime(&ms, s.ev[4], s.ev[5]) == hipSuccess) s.filter_ms = ms;
+    s.cur ^= 1;
+    s.mom_valid = true;
+    s.have_result = true;
 }
 
 static SvgfState* result_state(const char* who, rtg_handle* h) {
@@ -370,78 +442,22 @@ int rtg_svgf_accumulate(rtg_handle* h, const rtg_svgf_params* p, float* out) {
     if (int rc = denoise_state(h)) return rc;
     SvgfState& s = *t.sv;
     hipStream_t st = h->stream;
-    const dim3 grid((unsigned)(h->W + 63) / 64, (unsigned)(h->H + 3) / 4);
-    SvgfTemporalArgs a{};
-    const bool unchanged = temporal_setup(h, t, p->temporal, a);
-    a.mom_on = (t.have_hist && s.mom_valid) ? 1 : 0;
-    a.mom_in = s.mom[s.cur].p;
-    a.mom_out = s.mom[s.cur ^ 1].p;
     const float4* g = nullptr;  // the current geometry guide: the history's own when the camera is its camera
-    bool traced = false;
+    bool traced = false, unchanged = false;
     HIPOK(hipEventRecord(s.ev[0], st));
     // one fused first-hit pass for the geometry guide and the denoiser's guides (nothing when both are at hand);
     // it renders nothing, so the statistics have nothing to be put back
     if (int rc = current_guide(h, true, &g, &traced)) return rc;
     HIPOK(hipEventRecord(s.ev[1], st));
-    if (a.mode == 2) a.gcur = g;
-    HIPOK(hipEventRecord(s.ev[2], st));
-    hipLaunchKernelGGL(k_svgf_temporal, grid, dim3(256), 0, st, a);
-    LAUNCH_OK("k_svgf_temporal");
-    HIPOK(hipEventRecord(s.ev[3], st));
-
-    SvgfVarianceArgs v{};
-    v.hist = a.hout;
-    v.mom = a.mom_out;
-    v.geo = g;
-    v.col = s.col[0].p;
-    v.var = s.var.p;
-    v.W = h->W;
-    v.H = h->H;
-    v.min_history = p->min_history;
-    v.plane_tolerance = p->temporal.plane_tolerance;
-    v.normal_cos = p->temporal.normal_cos;
-    hipLaunchKernelGGL(k_svgf_variance, grid, dim3(256), 0, st, v);
-    LAUNCH_OK("k_svgf_variance");
-    HIPOK(hipEventRecord(s.ev[4], st));
-
-    const dim3 lin((unsigned)((t.n + 255) / 256));
-    hipLaunchKernelGGL(k_svgf_pack_pos, lin, dim3(256), 0, st, g, t.n, s.xpos.p);
-    LAUNCH_OK("k_svgf_pack_pos");
-    SvgfFilterArgs f{};
-    f.guide = h->dn->guide.p;
-    f.geo = g;
-    f.xpos = s.xpos.p;
-    f.W = h->W;
-    f.H = h->H;
-    f.m = (int)p->normal_squarings;
-    f.alb_on = p->sigma_albedo > 0.0f;
-    f.s2 = p->sigma_luminance * p->sigma_luminance;
-    f.floor = p->variance_floor;
-    f.ia = f.alb_on ? 1.0f / (p->sigma_albedo * p->sigma_albedo) : 0.0f;
-    f.plane_tolerance = p->temporal.plane_tolerance;
-    for (uint32_t i = 0; i < p->iterations; ++i) {
-        f.cin = s.col[i & 1].p;
-        f.cout = s.col[(i + 1) & 1].p;
-        f.step = 1 << i;
-        hipLaunchKernelGGL(k_svgf_atrous, grid, dim3(256), 0, st, f);
-        LAUNCH_OK("k_svgf_atrous");
-    }
-    HIPOK(hipEventRecord(s.ev[5], st));
-    hipLaunchKernelGGL(k_svgf_unpack, lin, dim3(256), 0, st,
+    if (int rc = svgf_queue(h, p, t, s, h->d_film, g, &unchanged)) return rc;
+    hipLaunchKernelGGL(k_svgf_unpack, dim3((unsigned)((t.n + 255) / 256)), dim3(256), 0, st,
                        (const float4*)s.col[p->iterations & 1].p, t.n, s.out.p);
     LAUNCH_OK("k_svgf_unpack");
     if (out) HIPOK(hipMemcpyAsync(out, s.out.p, t.n * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
     HIPOK(hipStreamSynchronize(st));
-    float ms = 0.0f;
-    s.guide_ms = stage_ms(traced, s.ev[0], s.ev[1]);
+    svgf_done(s, traced);
     t.gbuffer_ms = s.guide_ms;
-    if (hipEventElapsedTime(&ms, s.ev[2], s.ev[3]) == hipSuccess) s.accumulate_ms = ms;
-    if (hipEventElapsedTime(&ms, s.ev[3], s.ev[4]) == hipSuccess) s.variance_ms = ms;
-    if (hipEventElapsedTime(&ms, s.ev[4], s.ev[5]) == hipSuccess) s.filter_ms = ms;
     temporal_advance(h, unchanged, g);
-    s.cur ^= 1;
-    s.mom_valid = true;
-    s.have_result = true;
     return RTG_OK;
 }
 

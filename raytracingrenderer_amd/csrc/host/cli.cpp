@@ -52,6 +52,13 @@
 // denoiser's guides: first-hit albedo and |shading normal|) and PREFIX_depth.hdr (the first hit's distance t in
 // all three channels, 0 on a miss) as RGBE, from one traversal of the pixel-centre camera rays; with -from / -to
 // / -up / -fov they are the AOVs of that pose. One device only.
+// Frame loop with poses (Main.cpp:74-118 with a camera that moves; rtg_svgf_accumulate): -orbit "N DEG" runs N
+// poses on an arc of DEG degrees about the centre of the scene's bounds (axis: the up vector), starting at the
+// scene's (or -from's) position and looking at that centre (tests/temporal_ref.py: orbit, in binary64). Per pose i:
+// rtg_set_camera, rtg_clear, -SPP samples under seed + i, then rtg_svgf_accumulate, or with -svgfIllum 1
+// rtg_svgf_illum_accumulate. -svgfPlaneTolerance x sets plane_tolerance (default 0.01). The last
+// pose's film is written as above, the filtered image of the last pose as <name>_svgf.hdr (<name> as for
+// _denoised). No time limit. One device only.
 // Multi-GPU (one node): -gpus N renders on devices 0..N-1, -devices a,b,... on a list. Rank r
 // renders the 32x32 tiles with (tile_x + tile_y) % N == r, and the film is assembled on the first
 // device from every device's own tiles (packed, one RCCL send per device, scattered) before it is
@@ -61,6 +68,7 @@
 #include "../../../include/rth.h"
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <sstream>
 #include <cstdlib>
@@ -183,6 +191,49 @@ int main(int argc, char** argv) {
     }
     const std::string aov = get("-aov", "");
     if (!aov.empty() && !devices.empty()) return die("-aov", "one device only (not with -gpus / -devices)");
+    // -orbit "N DEG": the poses of the frame loop (temporal_ref.orbit)
+    std::vector<std::pair<rtg_camera, rtg_camera_proj>> orbit;
+    if (args.count("-orbit")) {
+        if (!devices.empty()) return die("-orbit", "one device only (not with -gpus / -devices)");
+        std::stringstream os(args["-orbit"]);
+        int n_poses = 0;
+        double total_deg = 0.0;
+        std::string rest;
+        if (!(os >> n_poses >> total_deg) || (os >> rest) || n_poses < 1) return die("-orbit", "a count and an angle, as \"N DEG\"");
+        float from[3], to[3], up[3], fov = 0.0f;
+        int32_t flip_x = 0;
+        if (rth_scene_camera_pose(scene, from, to, up, &fov, &flip_x) != 0) return die("camera pose", rth_last_error());
+        auto vec3 = [&](const char* k, float* v) {
+            if (!args.count(k)) return true;
+            std::stringstream ss(args[k]);
+            return bool(ss >> v[0] >> v[1] >> v[2]);
+        };
+        if (!vec3("-from", from) || !vec3("-up", up)) return die("-orbit", "-from and -up take three numbers");
+        if (args.count("-fov")) fov = std::stof(args["-fov"]);
+        double c[3], v[3], k[3];
+        for (int a = 0; a < 3; ++a) {
+            c[a] = 0.5 * ((double)info.bounds_min[a] + (double)info.bounds_max[a]);
+            v[a] = (double)from[a] - c[a];
+            k[a] = up[a];
+        }
+        const double kl = std::sqrt((k[0] * k[0] + k[1] * k[1]) + k[2] * k[2]);
+        for (double& x : k) x /= kl;
+        const double kv = (k[0] * v[0] + k[1] * v[1]) + k[2] * v[2];
+        const double cr[3] = {k[1] * v[2] - k[2] * v[1], k[2] * v[0] - k[0] * v[2], k[0] * v[1] - k[1] * v[0]};
+        for (int i = 0; i < n_poses; ++i) {  // Rodrigues' rotation of from - c about up
+            const double ang = (total_deg * i / std::max(n_poses - 1, 1)) * (M_PI / 180.0);
+            float f[3], t[3];
+            for (int a = 0; a < 3; ++a) {
+                f[a] = (float)(c[a] + ((v[a] * std::cos(ang) + cr[a] * std::sin(ang)) + k[a] * kv * (1 - std::cos(ang))));
+                t[a] = (float)c[a];
+            }
+            rtg_camera oc{};
+            rtg_camera_proj op{};
+            if (rth_camera_look_at(f, t, up, fov, info.width, info.height, flip_x, &oc, &op) != 0)
+                return die("rth_camera_look_at", rth_last_error());
+            orbit.emplace_back(oc, op);
+        }
+    }
     rtg_handle* rt = nullptr;
     rtg_group* grp = nullptr;
     if (devices.empty()) {
@@ -224,6 +275,27 @@ int main(int argc, char** argv) {
     unsigned spp = 0;
     double total = 0.0;
     const auto w0 = std::chrono::steady_clock::now();
+    std::vector<float> filtered;
+    if (!orbit.empty()) {  // the frame loop with poses: move, clear, render, filter
+        const bool illum = std::stoi(get("-svgfIllum", "0")) != 0;
+        rtg_svgf_illum_params ip{};
+        rtg_svgf_illum_defaults(&ip);
+        ip.svgf.temporal.plane_tolerance = std::stof(get("-svgfPlaneTolerance", std::to_string(ip.svgf.temporal.plane_tolerance)));
+        filtered.resize((size_t)info.width * info.height * 3);
+        for (size_t i = 0; i < orbit.size(); ++i) {
+            auto t0 = std::chrono::steady_clock::now();
+            if (rtg_set_camera(rt, &orbit[i].first, &orbit[i].second) != 0) return die("rtg_set_camera", rtg_last_error());
+            if (rtg_clear(rt) != 0) return die("rtg_clear", rtg_last_error());
+            if (rtg_render(rt, 0, spp_target, seed + i, nullptr, 0) != 0) return die("rtg_render", rtg_last_error());
+            if ((illum ? rtg_svgf_illum_accumulate(rt, &ip, filtered.data())
+                       : rtg_svgf_accumulate(rt, &ip.svgf, filtered.data())) != 0)
+                return die(illum ? "rtg_svgf_illum_accumulate" : "rtg_svgf_accumulate", rtg_last_error());
+            const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            total += dt;
+            std::printf("Pose %zu | Frame time: %gs | Total time: %gs\n", i, dt, total);
+        }
+        spp = spp_target;
+    }
     while (spp < spp_target) {
         const unsigned n = std::min(batch, spp_target - spp);
         auto t0 = std::chrono::steady_clock::now();
@@ -279,6 +351,15 @@ int main(int argc, char** argv) {
         if (rth_save_hdr(den_name.c_str(), info.width, info.height, den.data(), 1) != 0)  // already a mean
             return die("saveHDR", rth_last_error());
         std::printf("wrote %s\n", den_name.c_str());
+    }
+    if (!filtered.empty()) {
+        std::string base = out_given ? filename : auto_name;
+        const size_t dot = base.find_last_of('.'), slash = base.find_last_of('/');
+        if (dot != std::string::npos && (slash == std::string::npos || dot > slash)) base.erase(dot);
+        const std::string name = base + "_svgf.hdr";
+        if (rth_save_hdr(name.c_str(), info.width, info.height, filtered.data(), 1) != 0)  // already a mean
+            return die("saveHDR", rth_last_error());
+        std::printf("wrote %s\n", name.c_str());
     }
     if (!aov.empty()) {
         const size_t n = (size_t)info.width * info.height;

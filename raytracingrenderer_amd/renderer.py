@@ -190,6 +190,25 @@ def svgf_defaults():
             "variance_floor": p.variance_floor}
 
 
+def svgf_illum_check(albedo_floor=1e-3, **svgf):
+    """rtg_svgf_illum_check: the argument check of RayTracer.svgf(illumination=True) alone (no device needed);
+    the other keywords are svgf_check's."""
+    d = svgf_defaults()
+    d.update(svgf)
+    p = N.rtg_svgf_illum_params(_svgf_params(**d), float(albedo_floor))
+    _check(N.rtg().rtg_svgf_illum_check(C.byref(p)), N.rtg().rtg_last_error)
+
+
+def svgf_illum_defaults():
+    p = N.rtg_svgf_illum_params()
+    _check(N.rtg().rtg_svgf_illum_defaults(C.byref(p)), N.rtg().rtg_last_error)
+    s = p.svgf
+    return {"max_history": s.temporal.max_history, "plane_tolerance": s.temporal.plane_tolerance,
+            "normal_cos": s.temporal.normal_cos, "iterations": s.iterations, "normal_squarings": s.normal_squarings,
+            "sigma_luminance": s.sigma_luminance, "sigma_albedo": s.sigma_albedo, "min_history": s.min_history,
+            "variance_floor": s.variance_floor, "albedo_floor": p.albedo_floor}
+
+
 def write_synthetic_scene(out_dir, n_tris=1_000_000, seed=20251015, width=1024, height=1024):
     """C3 synthetic scene as .gem + scene.json + albedo.png + env.hdr."""
     os.makedirs(out_dir, exist_ok=True)
@@ -556,40 +575,72 @@ class RayTracer:
         return g.value, a.value
 
     def svgf(self, max_history=64.0, plane_tolerance=0.01, normal_cos=0.9, iterations=5, normal_squarings=5,
-             sigma_luminance=4.0, sigma_albedo=0.1, min_history=4.0, variance_floor=1e-8):
+             sigma_luminance=4.0, sigma_albedo=0.1, min_history=4.0, variance_floor=1e-8, illumination=False,
+             albedo_floor=1e-3):
         """Variance-guided filtering of the temporal history (rtg_svgf_accumulate): temporal()'s step on the
         same history, a moments history next to it, a per-pixel variance (spatial below min_history) and
         `iterations` a-trous levels whose luminance term that variance scales, all on the device. The loop is:
         move, clear(), render(), svgf(). Returns the (H, W, 3) float32 image; the film, SPP and the settings
-        stay as they were. Waits for queued frames first."""
+        stay as they were. Waits for queued frames first.
+        illumination=True (rtg_svgf_illum_accumulate): the same chain on the film over the first hit's albedo
+        (channels at or below albedo_floor are not divided), multiplied back at the end, with directly seen
+        emitters in a class of their own, over a history of the mode's own: temporal_history() and the default
+        mode's state are not touched by it, nor its state by them."""
         out = np.zeros((self.height, self.width, 3), np.float32)
         p = _svgf_params(max_history, plane_tolerance, normal_cos, iterations, normal_squarings, sigma_luminance,
                          sigma_albedo, min_history, variance_floor)
+        if illumination:
+            q = N.rtg_svgf_illum_params(p, float(albedo_floor))
+            _check(self._lib.rtg_svgf_illum_accumulate(self._h, C.byref(q), N.ptr(out, C.c_float)),
+                   self._lib.rtg_last_error)
+            return out
         _check(self._lib.rtg_svgf_accumulate(self._h, C.byref(p), N.ptr(out, C.c_float)), self._lib.rtg_last_error)
         return out
 
-    def svgf_variance(self):
-        """The variance the last svgf() fed to its first level, (H, W) float32."""
+    def svgf_variance(self, illumination=False):
+        """The variance the last svgf() fed to its first level, (H, W) float32 (illumination: of that mode)."""
         out = np.zeros((self.height, self.width), np.float32)
-        _check(self._lib.rtg_svgf_variance(self._h, N.ptr(out, C.c_float)), self._lib.rtg_last_error)
+        f = self._lib.rtg_svgf_illum_variance if illumination else self._lib.rtg_svgf_variance
+        _check(f(self._h, N.ptr(out, C.c_float)), self._lib.rtg_last_error)
         return out
 
-    def svgf_moments(self):
-        """The moments history, (H, W, 2) float32: the first two moments of the luminance."""
+    def svgf_moments(self, illumination=False):
+        """The moments history, (H, W, 2) float32: the first two moments of the luminance (illumination: of that
+        mode's demodulated film)."""
         out = np.zeros((self.height, self.width, 2), np.float32)
-        _check(self._lib.rtg_svgf_moments(self._h, N.ptr(out, C.c_float)), self._lib.rtg_last_error)
+        f = self._lib.rtg_svgf_illum_moments if illumination else self._lib.rtg_svgf_moments
+        _check(f(self._h, N.ptr(out, C.c_float)), self._lib.rtg_last_error)
         return out
 
-    def copy_svgf_to(self, device_ptr):
-        """The last svgf() result, (H, W, 3) float32, copied to device memory on this GPU."""
-        _check(self._lib.rtg_svgf_copy_device(self._h, C.c_void_p(device_ptr)), self._lib.rtg_last_error)
+    def copy_svgf_to(self, device_ptr, illumination=False):
+        """The last svgf() result (illumination: of that mode), (H, W, 3) float32, copied to device memory on
+        this GPU."""
+        f = self._lib.rtg_svgf_illum_copy_device if illumination else self._lib.rtg_svgf_copy_device
+        _check(f(self._h, C.c_void_p(device_ptr)), self._lib.rtg_last_error)
 
-    def svgf_ms(self):
+    def svgf_ms(self, illumination=False):
         """(guide_ms, accumulate_ms, variance_ms, filter_ms): device time of the last svgf()'s guide pass (0
-        when none ran), temporal + moments kernel, variance kernel and filter levels together."""
-        v = [C.c_double() for _ in range(4)]
-        _check(self._lib.rtg_svgf_ms(self._h, *[C.byref(x) for x in v]), self._lib.rtg_last_error)
+        when none ran), temporal + moments kernel, variance kernel and filter levels together. illumination:
+        that mode's last call, with (prepare_ms, unpack_ms) of its two own kernels appended."""
+        v = [C.c_double() for _ in range(6 if illumination else 4)]
+        f = self._lib.rtg_svgf_illum_ms if illumination else self._lib.rtg_svgf_ms
+        _check(f(self._h, *[C.byref(x) for x in v]), self._lib.rtg_last_error)
         return tuple(x.value for x in v)
+
+    def svgf_illum_history(self):
+        """The illumination mode's history, (H, W, 4) float32: the demodulated rgb and len."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        _check(self._lib.rtg_svgf_illum_history(self._h, N.ptr(out, C.c_float)), self._lib.rtg_last_error)
+        return out
+
+    def svgf_illum_guide(self):
+        """(pos_t, normal_id) as geometry_guide() gives them, of the illumination history's camera and classed:
+        a pixel whose first hit is an emitter carries the miss records."""
+        a = np.zeros((self.height, self.width, 4), np.float32)
+        b = np.zeros((self.height, self.width, 4), np.float32)
+        _check(self._lib.rtg_svgf_illum_guide(self._h, N.ptr(a, C.c_float), N.ptr(b, C.c_float)),
+               self._lib.rtg_last_error)
+        return a, b
 
     def gbuffer(self):
         """The first-hit AOVs of the current camera from one traversal of its pixel-centre rays (rtg_gbuffer):
